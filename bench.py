@@ -2,6 +2,13 @@
 """Device-resident Eden encode+decode throughput (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the line.  `--full`
+adds, after the timed steps, what else the line can carry: the per-kernel
+profile, the quality check (check_rel_l2), the committed PMC traffic, the CPU
+baselines and the secondary workloads ("also").  `--dump-outputs DIR` writes
+what the last timed step computed (dump_outputs below).
 
 One step = Eden-encode every tensor of the workload (fp32 arena in HBM ->
 bit planes + scales in HBM) and decode them back (-> fp32 arena in HBM), the
@@ -49,6 +56,13 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="llama3_8b_fp32_update")
     ap.add_argument("--n-bits", type=int, default=8)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can carry: the per-kernel "
+                         "profile, the quality check, the committed PMC traffic, the CPU baselines and the "
+                         "--also workloads (the options below that shape them only matter with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (a fixed, seeded sample of y and of the "
+                         "bit planes, every scale) as DIR/<name>.npy")
     ap.add_argument("--cpu-budget-s", type=float, default=15.0,
                     help="CPU baseline: oracle time budget on the main workload's tensors")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -75,6 +89,16 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true", help="sharding + rank plumbing only (CPU, gloo)")
     ap.add_argument("--master-port", type=int, default=0)
     return ap.parse_args(argv)
+
+
+FULL_ONLY = ("also", "also_steps", "cpu_budget_s", "no_cpu_baseline", "no_kc_numa_variant", "no_kernel_events",
+             "traffic_json", "profile_steps")
+
+
+def full_only_given(args):
+    """The options given that shape only what --full runs."""
+    default = parse_args([])
+    return ["--" + n.replace("_", "-") for n in FULL_ONLY if getattr(args, n) != getattr(default, n)]
 
 
 # --------------------------------------------------------------- launcher ---
@@ -489,6 +513,49 @@ def kc_cpu_baseline(x, offs, numels, cores, per=KC_CPU_SAMPLE, ntens=4):
                       f"backward {t_b:.2f} s, wire ratio {zb / nb:.4f}; extrapolated linearly to the 1 GiB set"}
 
 
+# ------------------------------------------------------------ output dump ---
+DUMP_SAMPLE = 1 << 22  # sampled positions per large array (16 MiB as float32)
+
+
+def _sample_positions(segments, k, seed):
+    """Positions inside the (offset, length) segments of an array: all of them
+    when the segments hold at most k elements, else k of them drawn by a
+    seeded generator, sorted.  They depend on the segments alone."""
+    offs = np.asarray([o for o, _ in segments], np.int64)
+    lens = np.asarray([n for _, n in segments], np.int64)
+    ends = np.cumsum(lens)
+    total = int(ends[-1]) if len(ends) else 0
+    if total <= k:
+        flat = np.arange(total, dtype=np.int64)
+    else:
+        flat = np.sort(np.random.default_rng(seed).integers(0, total, size=k, dtype=np.int64))
+    seg = np.searchsorted(ends, flat, side="right")
+    return offs[seg] + flat - (ends[seg] - lens[seg])
+
+
+def dump_outputs(dirname, plan, y, planes, scales, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed step receives, as its last
+    timed step left it -- the decoded arena y, the encoder's bit planes and
+    per-slice scales -- as float32 DIR/<name>.npy (<name>_rank<r> with several
+    ranks).  y and the planes are sampled at DUMP_SAMPLE positions each,
+    inside the tensors' own ranges (the padding between them is never
+    written); the scales are whole.  Same arguments: same inputs, same
+    positions, so two builds compare output for output."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+
+    def take(t, segments, seed):
+        pos = torch.from_numpy(_sample_positions(list(segments), DUMP_SAMPLE, seed)).to(t.device)
+        return t.index_select(0, pos).to(torch.float32).cpu().numpy()
+    arrays = {"y": take(y, zip(plan.elem_offsets, plan.numels), 20240601),
+              "planes": take(planes, zip(plan.planes_offsets, plan.planes_nbytes), 20240602),
+              "scales": scales[:plan.n_slices].cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{tag}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 # ---------------------------------------------------------------- dry run ---
 def dry_run(args, rank, world):
     import torch.distributed as dist
@@ -535,6 +602,9 @@ def main(argv=None):
     if args.dry_run:
         dry_run(args, rank, world)
         return 0
+    if rank == 0 and not args.full and full_only_given(args):
+        print(f"bench.py: {', '.join(full_only_given(args))} only matter with --full; ignored in this plain run",
+              file=sys.stderr)
 
     import torch
     import torch.distributed as dist
@@ -598,7 +668,8 @@ def main(argv=None):
     # schedule: with two streams a launch's events also span the other
     # stream's kernel it waits behind (a serialized profile pass follows)
     two = plan.n_streams == 2
-    if not args.no_kernel_events and not two:
+    kernel_events = args.full and not args.no_kernel_events
+    if kernel_events and not two:
         plan.profile(True)
     ev0 = torch.cuda.Event(enable_timing=True)
     ev1 = torch.cuda.Event(enable_timing=True)
@@ -619,11 +690,18 @@ def main(argv=None):
     gpu_ms = ev0.elapsed_time(ev1)
     elapsed = max_over_ranks(elapsed, dev)
 
+    # the last timed step's outputs, before anything below runs the codec again
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, plan, y, planes, scales, rank, world)
+
+    # Everything from here to the result line but the throughput arithmetic
+    # is --full only: a plain run times its steps and reports them.
     # per-kernel breakdown: events of the timed region (one stream), or of a
     # serialized profile pass over the same tensors (two streams)
     kernels = {}
     kernels_source = None
-    if not args.no_kernel_events and numels:
+    if kernel_events and numels:
         pplan, pws = plan, ws
         if two:
             pplan = EdenPlan(numels, args.n_bits, wave_mib=args.wave_mib, streams=1)
@@ -655,9 +733,11 @@ def main(argv=None):
             del pplan, pws
 
     # quality check (not timed): relative L2 error of decode(encode(x))
-    with torch.no_grad():
-        rel = float(torch.linalg.vector_norm((y - x).double()) / torch.linalg.vector_norm(x.double())) \
-            if numels else 0.0
+    rel = None
+    if args.full:
+        with torch.no_grad():
+            rel = float(torch.linalg.vector_norm((y - x).double()) / torch.linalg.vector_norm(x.double())) \
+                if numels else 0.0
 
     in_bytes_rank = 4 * sum(numels)
     value = throughput_gib_s(in_bytes_rank, world, args.steps, elapsed, args.scaling, 4 * sum(sizes))
@@ -669,7 +749,9 @@ def main(argv=None):
     traffic_src = args.traffic_json
     default_sched = (args.wave_mib is None and args.streams is None
                      and not any(k.startswith("OFL_EDEN_") for k in os.environ))
-    if traffic_src is None and args.workload == "llama3_8b_fp32_update" and args.n_bits == 8 \
+    if not args.full:
+        traffic_src = None
+    elif traffic_src is None and args.workload == "llama3_8b_fp32_update" and args.n_bits == 8 \
             and world == 1 and default_sched:
         # PMC counters cannot be read from inside this process: the committed
         # rocprofv3 --pmc passes of this same workload and default schedule
@@ -716,7 +798,7 @@ def main(argv=None):
                            for n, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms"])}
 
     also = {}
-    if world == 1 and args.also:
+    if args.full and world == 1 and args.also:
         for name in [a for a in args.also.split(",") if a]:
             if name == "kc_uniform_1gib":
                 also[name] = kc_pipeline(max(10, args.also_steps // 2), 4, dev)
@@ -731,7 +813,7 @@ def main(argv=None):
     out = None
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             def x_host(i):
                 j = mine.index(i)
                 off = plan.elem_offsets[j]
@@ -739,7 +821,7 @@ def main(argv=None):
             cpu = cpu_baseline(shapes, x_host, args.n_bits, args.cpu_budget_s, indices=mine)
         out = {
             "metric": METRIC, "value": round(value, 2), "unit": "GiB/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
+            "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": "f32",
@@ -753,11 +835,12 @@ def main(argv=None):
                                        if args.scaling == "weak" else
                                        f"one update set, per-tensor LPT shards over {world} GPU(s)")},
             "gpu_ms_per_step_rank0": round(gpu_ms / args.steps, 3),
-            "check_rel_l2": round(rel, 6),
+            "check_rel_l2": None if rel is None else round(rel, 6),
             "roofline": roof,
             "cpu_baseline": cpu,
             "host_env": host_env,
             "also": also or None,
+            "dumped": dumped and {"dir": args.dump_outputs, "arrays": dumped},
         }
         print(json.dumps(out), flush=True)
     if world > 1:

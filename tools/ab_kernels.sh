@@ -4,14 +4,15 @@
 # or NAME=VALUE (an environment setting for that run).  The default build
 # runs first.  Usage: tools/ab_kernels.sh [lib.so | VAR=value ...]
 set -e
-mkdir -p gpurun_out
+export O=${AB_OUT:-ab_out}  # exported: run() is re-declared in a child bash below
+mkdir -p "$O"
 run() {
   local tag=$1
-  timeout -k 10 240 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --also "" ${AB_ARGS:-} > gpurun_out/ab_$tag.json 2> gpurun_out/ab_$tag.err
-  python - "$tag" <<'PY'
+  timeout -k 10 240 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --also "" ${AB_ARGS:-} > "$O/ab_$tag.json" 2> "$O/ab_$tag.err"
+  python - "$tag" "$O" <<'PY'
 import json, sys
-tag = sys.argv[1]
-d = json.loads([l for l in open(f"gpurun_out/ab_{tag}.json") if l.startswith("{")][-1])
+tag, out = sys.argv[1:3]
+d = json.loads([l for l in open(f"{out}/ab_{tag}.json") if l.startswith("{")][-1])
 print(f"== {tag}: {d['value']} GiB/s  {d['ms_per_step']} ms/step")
 for k, v in d["roofline"]["kernels"].items():
     if v["share"] > 0.01:

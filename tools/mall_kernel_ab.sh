@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/$TAG
 mkdir -p "$R/$O"
 for m in 2048 128 64; do
-  timeout -k 10 120 python -u bench.py --workload uniform_1gib --also "" --no-cpu-baseline --streams 1 \
+  timeout -k 10 120 python -u bench.py --full --workload uniform_1gib --also "" --no-cpu-baseline --streams 1 \
       --wave-mib $m --steps 20 --warmup 3 > "$R/$O/bench_w$m.json" 2> "$R/$O/bench_w$m.err"
   echo "events w$m done"
   PMC_PASSES=traffic timeout -k 10 300 bash tools/pmc_run.sh "$O/pmc_w$m" --workload uniform_1gib --also "" \

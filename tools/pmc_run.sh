@@ -18,5 +18,5 @@ fi
 for pmc in "${PASSES[@]}"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $pmc --output-format csv -d "$OUT/pass$i" -o p -- \
-      python "$R/bench.py" --no-cpu-baseline --no-kernel-events "$@" > "$OUT/pass$i.log" 2>&1
+      python "$R/bench.py" --full --no-cpu-baseline --no-kernel-events "$@" > "$OUT/pass$i.log" 2>&1
 done

@@ -19,5 +19,5 @@ T 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/kc_pmc/pass1 -o p -- 
 T 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/kc_pmc/pass2 -o p -- python3 $R/tools/kc_bench.py --steps 3 --warmup 1 > $O/kc_pmc2.log 2>&1 || exit 26
 cd $R && python tools/pmc_traffic.py $O/kc_pmc 4 $O/kc_traffic.json > /dev/null || exit 27
 cp $O/kc_traffic.json profiles/r04_final_kc_pipeline_hbm_traffic.json
-T 600 python -u bench.py > $O/bench.json 2> $O/bench.err || exit 14
+T 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit 14
 echo "kc final done"

@@ -20,11 +20,11 @@ rc=$?; echo "pytest rc=$rc" >> $O/pytest_gpu.log
 [ $rc -eq 0 ] || exit 11
 PMC_PASSES=traffic T 600 bash tools/pmc_run.sh gpurun_out/evidence_$TAG/pmc --steps 5 --warmup 2 --also "" || exit 12
 python tools/pmc_traffic.py $O/pmc 7 $O/hbm_traffic.json > /dev/null || exit 13
-T 600 python -u bench.py --traffic-json $O/hbm_traffic.json > $O/bench.json 2> $O/bench.err || exit 14
+T 600 python -u bench.py --full --traffic-json $O/hbm_traffic.json > $O/bench.json 2> $O/bench.err || exit 14
 echo "bench done"
 cd /tmp && export TMPDIR=/tmp
-T 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -o run -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --also "" > $O/bench_default_under_rocprof.json 2> $O/prof_default.err || exit 21
-T 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_1stream -o run -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --also "" --streams 1 > $O/bench_1stream_under_rocprof.json 2> $O/prof_1stream.err || exit 22
+T 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -o run -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --also "" > $O/bench_default_under_rocprof.json 2> $O/prof_default.err || exit 21
+T 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_1stream -o run -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --also "" --streams 1 > $O/bench_1stream_under_rocprof.json 2> $O/prof_1stream.err || exit 22
 cd $R
 echo "part a done"
 fi
@@ -36,7 +36,7 @@ T 400 python -u tools/e2e_bench.py --modes plugin,plugin_concurrent,batched,cpu 
 T 300 python -u tools/call_overhead_probe.py > $O/call_overhead.json 2> $O/call_overhead.err || exit 19
 T 200 python -u tools/sum_rate.py > $O/sum_rate.log 2>&1 || exit 20
 cd /tmp && export TMPDIR=/tmp
-T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_resnet -o run -- python3 $R/bench.py --workload resnet50_fp32 --steps 50 --warmup 10 --also "" --no-cpu-baseline --no-kernel-events > $O/resnet_under_rocprof.json 2> $O/prof_resnet.err || exit 23
+T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_resnet -o run -- python3 $R/bench.py --full --workload resnet50_fp32 --steps 50 --warmup 10 --also "" --no-cpu-baseline --no-kernel-events > $O/resnet_under_rocprof.json 2> $O/prof_resnet.err || exit 23
 T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kc_trace -o k -- python3 $R/tools/kc_bench.py --steps 3 --warmup 1 > $O/kc_trace.log 2>&1 || exit 24
 T 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/kc_pmc/pass1 -o p -- python3 $R/tools/kc_bench.py --steps 3 --warmup 1 > $O/kc_pmc1.log 2>&1 || exit 25
 T 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/kc_pmc/pass2 -o p -- python3 $R/tools/kc_bench.py --steps 3 --warmup 1 > $O/kc_pmc2.log 2>&1 || exit 26

@@ -10,5 +10,5 @@ rc=$?; echo "pytest rc=$rc" >> $O/pytest_gpu.log
 [ $rc -eq 0 ] || exit 11
 T 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || exit 12
 
-T 600 python -u bench.py > $O/bench.json 2> $O/bench.err || exit 13
+T 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || exit 13
 echo "bench done"

@@ -11,7 +11,7 @@ mkdir -p $O
 T() { timeout -k 10 "$@"; }
 run() {  # tag workload wave streams row2
   local tag=$1 wl=$2 w=$3 s=$4 r2=$5
-  OFL_EDEN_ROW2=$r2 T 200 python -u bench.py --workload $wl --also "" --no-cpu-baseline --wave-mib $w --streams $s \
+  OFL_EDEN_ROW2=$r2 T 200 python -u bench.py --full --workload $wl --also "" --no-cpu-baseline --wave-mib $w --streams $s \
       --steps 10 --warmup 3 > $O/$tag.json 2> $O/$tag.err
   local rc=$?
   echo "$tag rc=$rc $(python -c "import json;d=json.load(open('$O/$tag.json'));print(d['value'],d['ms_per_step'],d['roofline'].get('dominant_kernel',{}).get('name'))" 2>/dev/null)" >> $O/summary.txt

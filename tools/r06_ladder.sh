@@ -17,7 +17,7 @@ lib() { case $1 in full) echo $R/openfl_amd/lib/libofl_codec.so;; *) echo $R/too
 for l in lad1 lad2 lad3 full; do
   for w in 64 128 2048; do
     r2=1; [ $w = 2048 ] && r2=""
-    OFL_CODEC_LIB=$(lib $l) OFL_EDEN_ROW2=$r2 T 200 python -u bench.py --workload uniform_1gib --also "" \
+    OFL_CODEC_LIB=$(lib $l) OFL_EDEN_ROW2=$r2 T 200 python -u bench.py --full --workload uniform_1gib --also "" \
         --no-cpu-baseline --wave-mib $w --streams 1 --steps 10 --warmup 3 > $O/${l}_w$w.json 2> $O/${l}_w$w.err || exit 2
     echo "$l w$w $(python -c "import json;d=json.load(open('$O/${l}_w$w.json'));print(d['value'],d['ms_per_step'])")"
   done
@@ -29,7 +29,7 @@ for l in lad1 lad2 lad3 full; do
              "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_BUSY_CU_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_WAIT_INST_LDS"; do
     i=$((i+1))
     OFL_CODEC_LIB=$(lib $l) OFL_EDEN_ROW2=1 T 120 rocprofv3 --pmc $pmc --output-format csv -d $O/sq_${l}_w64/pass$i -o p -- \
-        python3 $R/bench.py --workload uniform_1gib --also "" --no-cpu-baseline --no-kernel-events --wave-mib 64 \
+        python3 $R/bench.py --full --workload uniform_1gib --also "" --no-cpu-baseline --no-kernel-events --wave-mib 64 \
         --streams 1 --steps 3 --warmup 1 > $O/sq_${l}_$i.log 2>&1 || exit 3
   done
   (cd $R && python tools/pmc_kernels.py $O/sq_${l}_w64 $O/sq_${l}_w64.json k_enc k_dec k_col > /dev/null) || exit 4

@@ -13,7 +13,7 @@ run() {  # tag env... -- bench args
   local tag=$1; shift
   local envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 200 python -u bench.py --also "" --no-cpu-baseline --no-kernel-events "$@" > $O/$tag.json 2> $O/$tag.err || exit 2
+  env "${envs[@]}" timeout -k 10 200 python -u bench.py --full --also "" --no-cpu-baseline --no-kernel-events "$@" > $O/$tag.json 2> $O/$tag.err || exit 2
   echo "$tag $(python -c "import json;d=json.load(open('$O/$tag.json'));print(d['value'],d['ms_per_step'],d['gpu_ms_per_step_rank0'])")"
 }
 for rep in 1 2; do

@@ -12,7 +12,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 1
 rc=$?; echo "parity rc=$rc"; tail -n 2 $O/parity.log; [ $rc -eq 0 ] || exit 1
 b() {  # tag env -- args
   local tag=$1; shift; local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 300 python -u bench.py --also "" --no-cpu-baseline --no-kernel-events "$@" > $O/$tag.json 2> $O/$tag.err || exit 2
+  env "${envs[@]}" timeout -k 10 300 python -u bench.py --full --also "" --no-cpu-baseline --no-kernel-events "$@" > $O/$tag.json 2> $O/$tag.err || exit 2
   echo "$tag $(python -c "import json;d=json.load(open('$O/$tag.json'));print(d['value'],d['gpu_ms_per_step_rank0'],d['check_rel_l2'])")"
 }
 for rep in 1 2; do

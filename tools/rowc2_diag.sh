@@ -8,7 +8,7 @@ O=${1:-gpurun_out/rowc2_diag}
 mkdir -p "$O"
 run() {  # name lib
     if [ -n "$2" ]; then export OFL_CODEC_LIB="$2"; else unset OFL_CODEC_LIB; fi
-    timeout -k 10 240 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --also "" --streams 1 > "$O/$1.json" 2> "$O/$1.err"
+    timeout -k 10 240 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --also "" --streams 1 > "$O/$1.json" 2> "$O/$1.err"
     python - "$O/$1.json" "$1" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
