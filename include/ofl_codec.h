@@ -98,14 +98,20 @@ int ofl_eden_plan_num_waves(ofl_eden_plan_t plan);
  * outputs bit-identical either way): -1 auto (launches of fewer than 5 tiles
  * per CU use the two-blocks-per-CU kernels, the rest the persistent
  * prefetching ones; env OFL_EDEN_ROW2 / OFL_EDEN_ROW2_TPC override the auto
- * rule), 0 always persistent, 1 always two blocks per CU. */
+ * rule), 0 always persistent, 1 always two blocks per CU.  The schedule
+ * depends on it (a 5-pass slice above the wave size splits into sub-waves
+ * only with the two-blocks-per-CU kernels), so it is rebuilt: only before
+ * the plan's first encode/decode (OFL_EINVAL afterwards). */
 int ofl_eden_plan_set_row2(ofl_eden_plan_t plan, int mode);
 /* Tile pairs in the two-blocks-per-CU row passes that apply the D1 signs
  * (encode pass A, decode pass C; no reference counterpart, outputs
  * bit-identical either way): a block runs a tile and the one 2^(p-3)
  * elements up, whose sign words are the same, and hashes them once.
  * -1 auto (launches of more tiles than two per CU; env OFL_EDEN_PAIR
- * overrides), 0 never, 1 whenever the launch holds slices of >= 2^18. */
+ * overrides), 0 never, 1 whenever the launch holds slices of >= 2^18.
+ * The sub-waves of a split 5-pass slice get their paired tile tables when
+ * the schedule is built, so it is rebuilt: only before the plan's first
+ * encode/decode (OFL_EINVAL afterwards). */
 int ofl_eden_plan_set_pair(ofl_eden_plan_t plan, int mode);
 /* Launches of the tiny (<= 2^10) and small (2^11..2^15) slices (no reference
  * counterpart; outputs bit-identical either way): 1 one small-set launch of
@@ -246,6 +252,14 @@ int ofl_eden_plan_profile(ofl_eden_plan_t plan, int enable);
 int ofl_eden_plan_num_launches(ofl_eden_plan_t plan, int encode);
 int ofl_eden_plan_launch_info(ofl_eden_plan_t plan, int encode, int idx, char* name, int cap,
                               int64_t* blocks, int64_t* bytes_moved, int64_t* bytes_alg);
+/* How launch idx of a plain encode / decode runs (decided by the same code
+ * that launches it): explicit_tiles 1 when it walks an explicit tile list (a
+ * sub-wave of a split 5-pass slice), paired 1 when a row launch walks the
+ * paired tile table, grid the number of workgroups.  The weighted-average
+ * encode (ofl_eden_encode_wavg) runs the same launches, its pass A always
+ * unpaired.  Any out pointer may be null. */
+int ofl_eden_plan_launch_detail(ofl_eden_plan_t plan, int encode, int idx, int32_t* explicit_tiles,
+                                int32_t* paired, int64_t* grid);
 int ofl_eden_plan_profile_collect(ofl_eden_plan_t plan, int encode, double* ms_sum, int max,
                                   int* ncalls);
 

@@ -150,6 +150,11 @@ class EdenPlan:
         _lib.check(self._L.ofl_eden_plan_profile(self._h, 1 if enable else 0))
 
     def launches(self, encode):
+        """The launches of a plain encode / decode, in order: kernel name,
+        blocks (tiles / work items), HBM and algorithmic bytes, and what
+        ofl_eden_plan_launch_detail reports -- expl (over an explicit tile
+        list: a sub-wave of a split 5-pass slice), paired (that row launch
+        walks the paired tile table) and grid (workgroups launched)."""
         out = []
         for i in range(self._L.ofl_eden_plan_num_launches(self._h, 1 if encode else 0)):
             name = ctypes.create_string_buffer(128)
@@ -157,8 +162,12 @@ class EdenPlan:
             _lib.check(self._L.ofl_eden_plan_launch_info(self._h, 1 if encode else 0, i, name, 128,
                                                          ctypes.byref(blocks), ctypes.byref(mv),
                                                          ctypes.byref(al)))
+            expl, paired, grid = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+            _lib.check(self._L.ofl_eden_plan_launch_detail(self._h, 1 if encode else 0, i, ctypes.byref(expl),
+                                                           ctypes.byref(paired), ctypes.byref(grid)))
             out.append({"name": name.value.decode(), "blocks": blocks.value,
-                        "bytes_moved": mv.value, "bytes_alg": al.value})
+                        "bytes_moved": mv.value, "bytes_alg": al.value,
+                        "expl": bool(expl.value), "paired": bool(paired.value), "grid": grid.value})
         return out
 
     def profile_collect(self, encode):

@@ -2904,6 +2904,51 @@ bool use_colmulti() {
     return on;
 }
 
+// What a row launch (K_ROWA / K_ROWC) runs -- decided here alone, for run()
+// and for the names and details the plan reports (launch_name,
+// ofl_eden_plan_launch_detail).  wavg: the fused weighted-average encode's
+// pass A (k_enc_rowA2<true>), which never takes tile pairs.
+struct RowChoice {
+    bool two;      // the two-blocks-per-CU kernel (k_*_row?2), else the persistent one
+    bool expl;     // over an explicit tile list (a sub-wave of a split 5-pass slice)
+    bool paired;   // its table lists tile pairs
+    int tab_off;   // the table in ints that replaces the launch's default one (-1: keep)
+    int npair;     // table entries (KArgs::npair; 0: the launch's tile prefix)
+    int64_t grid;
+};
+RowChoice row_choice(const ofl_eden_plan* pl, const Launch& l, bool enc, bool wavg) {
+    const bool signs = l.kind == K_ROWA ? enc : !enc;  // the pass that applies D1
+    RowChoice c{false, l.expl, false, -1, 0, std::min<int64_t>(l.blocks, pl->ncu)};
+    if (l.expl) {
+        c.two = true;
+        c.paired = signs && !wavg && l.ptab_off >= 0;
+        c.tab_off = c.paired ? l.ptab_off : l.btab_off;
+        c.npair = c.paired ? l.npair : (int)l.expl_tiles;
+        c.grid = std::min<int64_t>(c.npair, 2 * pl->ncu);
+        return c;
+    }
+    if (l.kind == K_ROWA ? wavg || use_row2(l.blocks, pl->ncu, pl->row2)
+                         : (enc ? use_rowc2() : use_row2(l.blocks, pl->ncu, pl->row2))) {
+        c.two = true;
+        c.grid = std::min<int64_t>(l.blocks, 2 * pl->ncu);
+        if (signs && !wavg && use_pair(l, pl->ncu, pl->pair)) {
+            c.paired = true;
+            c.tab_off = l.ptab_off;
+            c.npair = l.npair;
+            c.grid = std::min<int64_t>(l.npair, 2 * pl->ncu);
+        }
+    }
+    return c;
+}
+
+// the kernel of a column launch (K_COL), for run() and launch_name
+enum ColKernel { COL_PLAIN, COL6, COL6_NT, COL6_TL16 };
+ColKernel col_choice(const Launch& l) {
+    if (l.tl == 16) return COL6_TL16;
+    if (l.nt && l.param == 7 && l.mid && col6_for(7, true)) return COL6_NT;
+    return col6_for(l.param, l.mid != 0) ? COL6 : COL_PLAIN;
+}
+
 hipError_t set_all_attrs() {
     hipError_t e;
     if ((e = set_small_attr<11>()) != hipSuccess) return e;
@@ -3017,73 +3062,36 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
         }
         case K_ROWA: {
             const bool a8 = l.mid && (reinterpret_cast<uintptr_t>(base.pin) & 7u) == 0;
-            if (l.expl) {  // a sub-wave of a split 5-pass slice: its tile list
-                const bool paired = enc && !base.wx && l.ptab_off >= 0;
-                a.btab = pl->d_ints + (paired ? l.ptab_off : l.btab_off);
-                a.npair = paired ? l.npair : (int)l.expl_tiles;
-                const int64_t g2 = std::min<int64_t>(a.npair, 2 * pl->ncu);
-                e = enc ? (base.wx ? launch(ofl::k_enc_rowA2<true>, g2, ofl::kRowNT, ofl::kRow2Smem, st, a)
-                                   : launch(ofl::k_enc_rowA2<false>, g2, ofl::kRowNT, ofl::kRow2Smem, st, a))
-                        : a8 ? launch(ofl::k_dec_rowA2<true>, g2, ofl::kRowNT, ofl::kRow2SmemC, st, a)
-                             : launch(ofl::k_dec_rowA2<false>, g2, ofl::kRowNT, ofl::kRow2SmemC, st, a);
-                break;
-            }
-            if (enc && base.wx) {  // fused round-end encode: x = the weighted-average delta
-                e = launch(ofl::k_enc_rowA2<true>, std::min<int64_t>(l.blocks, 2 * pl->ncu), ofl::kRowNT, ofl::kRow2Smem,
-                           st, a);
-                break;
-            }
-            if (use_row2(l.blocks, pl->ncu, pl->row2)) {
-                int64_t g2 = std::min<int64_t>(l.blocks, 2 * pl->ncu);
-                if (enc && use_pair(l, pl->ncu, pl->pair)) {
-                    a.btab = pl->d_ints + l.ptab_off;
-                    a.npair = l.npair;
-                    g2 = std::min<int64_t>(l.npair, 2 * pl->ncu);
-                }
-                e = enc ? launch(ofl::k_enc_rowA2<false>, g2, ofl::kRowNT, ofl::kRow2Smem, st, a)
-                        : a8 ? launch(ofl::k_dec_rowA2<true>, g2, ofl::kRowNT, ofl::kRow2SmemC, st, a)
-                             : launch(ofl::k_dec_rowA2<false>, g2, ofl::kRowNT, ofl::kRow2SmemC, st, a);
-                break;
-            }
-            const int64_t g = std::min<int64_t>(l.blocks, pl->ncu);
-            e = enc ? launch(ofl::k_enc_rowA, g, ofl::kRowNT, ofl::kRowSmemA, st, a)
-                    : a8 ? launch(ofl::k_dec_rowA<true>, g, ofl::kRowNT, ofl::kRowSmemC, st, a)
-                         : launch(ofl::k_dec_rowA<false>, g, ofl::kRowNT, ofl::kRowSmemC, st, a);
+            const RowChoice rc = row_choice(pl, l, enc, enc && base.wx);
+            if (rc.tab_off >= 0) a.btab = pl->d_ints + rc.tab_off;
+            a.npair = rc.npair;
+            if (rc.two)
+                e = enc ? (base.wx ? launch(ofl::k_enc_rowA2<true>, rc.grid, ofl::kRowNT, ofl::kRow2Smem, st, a)
+                                   : launch(ofl::k_enc_rowA2<false>, rc.grid, ofl::kRowNT, ofl::kRow2Smem, st, a))
+                        : a8 ? launch(ofl::k_dec_rowA2<true>, rc.grid, ofl::kRowNT, ofl::kRow2SmemC, st, a)
+                             : launch(ofl::k_dec_rowA2<false>, rc.grid, ofl::kRowNT, ofl::kRow2SmemC, st, a);
+            else
+                e = enc ? launch(ofl::k_enc_rowA, rc.grid, ofl::kRowNT, ofl::kRowSmemA, st, a)
+                        : a8 ? launch(ofl::k_dec_rowA<true>, rc.grid, ofl::kRowNT, ofl::kRowSmemC, st, a)
+                             : launch(ofl::k_dec_rowA<false>, rc.grid, ofl::kRowNT, ofl::kRowSmemC, st, a);
             break;
         }
         case K_ROWC: {
-            const int64_t g = std::min<int64_t>(l.blocks, pl->ncu);
-            if (l.expl) {  // a sub-wave of a split 5-pass slice: its tile list
-                const bool paired = !enc && l.ptab_off >= 0;
-                a.btab = pl->d_ints + (paired ? l.ptab_off : l.btab_off);
-                a.npair = paired ? l.npair : (int)l.expl_tiles;
-                const int64_t g2 = std::min<int64_t>(a.npair, 2 * pl->ncu);
-                e = !enc ? launch(ofl::k_dec_rowC2, g2, ofl::kRowNT, ofl::kRow2Smem, st, a)
-                    : use_roll() ? launch(ofl::k_enc_rowC2<true>, g2, ofl::kRowNT, ofl::kRowC2Smem, st, a)
-                                 : launch(ofl::k_enc_rowC2<false>, g2, ofl::kRowNT, ofl::kRowC2Smem, st, a);
-                break;
-            }
-            if (enc && use_rowc2())
-                e = use_roll() ? launch(ofl::k_enc_rowC2<true>, std::min<int64_t>(l.blocks, 2 * pl->ncu), ofl::kRowNT,
-                                        ofl::kRowC2Smem, st, a)
-                               : launch(ofl::k_enc_rowC2<false>, std::min<int64_t>(l.blocks, 2 * pl->ncu), ofl::kRowNT,
-                                        ofl::kRowC2Smem, st, a);
-            else if (!enc && use_row2(l.blocks, pl->ncu, pl->row2)) {
-                int64_t g2 = std::min<int64_t>(l.blocks, 2 * pl->ncu);
-                if (use_pair(l, pl->ncu, pl->pair)) {
-                    a.btab = pl->d_ints + l.ptab_off;
-                    a.npair = l.npair;
-                    g2 = std::min<int64_t>(l.npair, 2 * pl->ncu);
-                }
-                e = launch(ofl::k_dec_rowC2, g2, ofl::kRowNT, ofl::kRow2Smem, st, a);
-            }
+            const RowChoice rc = row_choice(pl, l, enc, false);
+            if (rc.tab_off >= 0) a.btab = pl->d_ints + rc.tab_off;
+            a.npair = rc.npair;
+            if (rc.two)
+                e = !enc ? launch(ofl::k_dec_rowC2, rc.grid, ofl::kRowNT, ofl::kRow2Smem, st, a)
+                    : use_roll() ? launch(ofl::k_enc_rowC2<true>, rc.grid, ofl::kRowNT, ofl::kRowC2Smem, st, a)
+                                 : launch(ofl::k_enc_rowC2<false>, rc.grid, ofl::kRowNT, ofl::kRowC2Smem, st, a);
             else
-                e = enc ? launch(ofl::k_enc_rowC, g, ofl::kRowNT, ofl::kRowSmemQ, st, a)
-                        : launch(ofl::k_dec_rowC, g, ofl::kRowNT, ofl::kRowSmemA, st, a);
+                e = enc ? launch(ofl::k_enc_rowC, rc.grid, ofl::kRowNT, ofl::kRowSmemQ, st, a)
+                        : launch(ofl::k_dec_rowC, rc.grid, ofl::kRowNT, ofl::kRowSmemA, st, a);
             break;
         }
         case K_COL: {
-            if (l.tl == 16) {  // 2^16-element tiles (M = 9, 10)
+            const ColKernel ck = col_choice(l);
+            if (ck == COL6_TL16) {  // 2^16-element tiles (M = 9, 10)
                 const size_t sm = col6_smem(l.param, l.mid != 0, 16);
                 e = l.param == 9 ? (l.mid ? launch(ofl::k_col6<9, true, 16>, l.blocks, 1024, sm, st, a)
                                           : launch(ofl::k_col6<9, false, 16>, l.blocks, 1024, sm, st, a))
@@ -3091,11 +3099,11 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
                                           : launch(ofl::k_col6<10, false, 16>, l.blocks, 1024, sm, st, a));
                 break;
             }
-            if (l.nt && l.param == 7 && l.mid && col6_for(7, true)) {
+            if (ck == COL6_NT) {
                 e = launch(ofl::k_col6<7, true, 15, true>, l.blocks, 512, col6_smem(7, true, 15), st, a);
                 break;
             }
-            if (col6_for(l.param, l.mid != 0)) {
+            if (ck == COL6) {
                 const size_t sm = col6_smem(l.param, l.mid != 0, 15);
 #define COL6CASE(MM)                                                                                 \
     case MM:                                                                                         \
@@ -3150,22 +3158,26 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
     return OFL_OK;
 }
 
-std::string launch_name(const Launch& l, bool enc, int ncu, int row2) {
+std::string launch_name(const ofl_eden_plan* pl, const Launch& l, bool enc) {
     const char* d = enc ? "enc" : "dec";
     switch (l.kind) {
     case K_TINY: return std::string("ofl::k_") + d + "_tiny";
     case K_SSET: return std::string("ofl::k_") + d + "_sset";
     case K_SMALL: return std::string("ofl::k_") + d + "_small<" + std::to_string(l.param) + ">";
-    case K_ROWA: return std::string("ofl::k_") + d + (use_row2(l.blocks, ncu, row2) ? "_rowA2" : "_rowA");
+    case K_ROWA: return std::string("ofl::k_") + d + (row_choice(pl, l, enc, false).two ? "_rowA2" : "_rowA");
     case K_ROWC:
-        if (enc && use_rowc2()) return std::string("ofl::k_enc_rowC2<") + (use_roll() ? "true" : "false") + ">";
-        if (!enc && use_row2(l.blocks, ncu, row2)) return "ofl::k_dec_rowC2";
-        return std::string("ofl::k_") + d + "_rowC";
-    case K_COL:
-        if (l.tl == 16) return "ofl::k_col6<" + std::to_string(l.param) + ", " + (l.mid ? "true" : "false") + ", 16>";
-        return std::string(col6_for(l.param, l.mid != 0) ? "ofl::k_col6<" : "ofl::k_col<") +
-               std::to_string(l.param) + ", " + (l.mid ? "true" : "false") +
-               (col6_for(l.param, l.mid != 0) ? ", 15>" : ">");
+        if (!row_choice(pl, l, enc, false).two) return std::string("ofl::k_") + d + "_rowC";
+        if (enc) return std::string("ofl::k_enc_rowC2<") + (use_roll() ? "true" : "false") + ">";
+        return "ofl::k_dec_rowC2";
+    case K_COL: {
+        const std::string mp = std::to_string(l.param) + ", " + (l.mid ? "true" : "false");
+        switch (col_choice(l)) {
+        case COL6_TL16: return "ofl::k_col6<" + mp + ", 16>";
+        case COL6_NT: return "ofl::k_col6<" + mp + ", 15, true>";
+        case COL6: return "ofl::k_col6<" + mp + ", 15>";
+        default: return "ofl::k_col<" + mp + ">";
+        }
+    }
     case K_COLM: return "ofl::k_col_multi";
     case K_COLMSET: return std::string("ofl::k_") + d + "_colm_set";
     default: return "ofl::k_finalize";
@@ -3862,7 +3874,9 @@ int ofl_eden_plan_set_row2(ofl_eden_plan_t pl, int mode) {
     if (!pl) return fail(OFL_EINVAL, "null plan");
     if (mode < -1 || mode > 1) return fail(OFL_EINVAL, "row2 mode must be -1 (auto), 0 or 1");
     std::lock_guard<std::mutex> g(pl->mu);
+    if (pl->uploaded) return fail(OFL_EINVAL, "row2 must be set before the plan's first encode/decode");
     pl->row2 = mode;
+    build_schedule(pl);
     return OFL_OK;
 }
 
@@ -3870,7 +3884,9 @@ int ofl_eden_plan_set_pair(ofl_eden_plan_t pl, int mode) {
     if (!pl) return fail(OFL_EINVAL, "null plan");
     if (mode < -1 || mode > 1) return fail(OFL_EINVAL, "pair mode must be -1 (auto), 0 or 1");
     std::lock_guard<std::mutex> g(pl->mu);
+    if (pl->uploaded) return fail(OFL_EINVAL, "pair must be set before the plan's first encode/decode");
     pl->pair = mode;
+    build_schedule(pl);
     return OFL_OK;
 }
 
@@ -4275,12 +4291,26 @@ int ofl_eden_plan_launch_info(ofl_eden_plan_t pl, int encode, int idx, char* nam
     const std::vector<Launch>& L = encode ? pl->enc : pl->dec;
     if (idx < 0 || idx >= (int)L.size()) return fail(OFL_EINVAL, "launch index out of range");
     if (name && cap > 0) {
-        const std::string s = launch_name(L[idx], encode != 0, pl->ncu, pl->row2);
+        const std::string s = launch_name(pl, L[idx], encode != 0);
         snprintf(name, (size_t)cap, "%s", s.c_str());
     }
     if (blocks) *blocks = L[idx].blocks;
     if (bytes_moved) *bytes_moved = L[idx].bytes_moved;
     if (bytes_alg) *bytes_alg = L[idx].bytes_alg;
+    return OFL_OK;
+}
+
+int ofl_eden_plan_launch_detail(ofl_eden_plan_t pl, int encode, int idx, int32_t* explicit_tiles, int32_t* paired,
+                                int64_t* grid) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    const std::vector<Launch>& L = encode ? pl->enc : pl->dec;
+    if (idx < 0 || idx >= (int)L.size()) return fail(OFL_EINVAL, "launch index out of range");
+    const Launch& l = L[idx];
+    const bool row = l.kind == K_ROWA || l.kind == K_ROWC;
+    const RowChoice rc = row ? row_choice(pl, l, encode != 0, false) : RowChoice{false, l.expl, false, -1, 0, l.blocks};
+    if (explicit_tiles) *explicit_tiles = l.expl ? 1 : 0;
+    if (paired) *paired = rc.paired ? 1 : 0;
+    if (grid) *grid = rc.grid;
     return OFL_OK;
 }
 

@@ -119,6 +119,20 @@ SIZES = [3, 64, 300, 1000, 2048, 3000, 4096, 8192, 12000, 16384, 16385, 1 << 15,
 @pytest.mark.parametrize("n", SIZES)
 @pytest.mark.parametrize("bits", [8, 3])
 def test_encode_decode_vs_oracle(n, bits):
+    _check_encode_decode_vs_oracle(n, bits)
+
+
+# The other bit widths on the large path (the goldens cover 1..8 bits only up
+# to 65 537 elements: one tile pair, aligned plane rows): a ragged 2^17 slice,
+# plane rows that are not 8-byte aligned (dims [2^21, 8]) and two column
+# levels.  Same bars.
+@pytest.mark.parametrize("n", [120_003, (1 << 21) + 7, 1 << 23])
+@pytest.mark.parametrize("bits", [1, 2, 4, 5, 6, 7])
+def test_encode_decode_vs_oracle_bit_widths(n, bits):
+    _check_encode_decode_vs_oracle(n, bits)
+
+
+def _check_encode_decode_vs_oracle(n, bits):
     x = np.random.default_rng(n + bits).standard_normal(n).astype(np.float32) * np.float32(0.01)
     seed = (n * 7 + bits) % 65536
     planes, scales, dims = gpu_encode(x, seed, bits)
@@ -266,28 +280,43 @@ def test_large_slice_property_2p29():
 
 # ------------------------------------------------------ batching / arenas ---
 def test_batch_equals_single():
+    _check_batch_equals_single([5, 1000, 4096, 70_000, 1 << 20, 3], 8)
+
+
+# At 3 bits the second plan puts an odd-length plane run (3 * (2^18 + 1) =
+# 786 435 bytes) in front of a large tensor.
+@pytest.mark.parametrize("numels", [[5, 1000, 4096, 70_000, 1 << 20, 3], [1000, (1 << 21) + 7, 3000, 1 << 20]],
+                         ids=["mixed", "odd_plane_runs"])
+@pytest.mark.parametrize("bits", [3, 5])
+def test_batch_equals_single_bits(bits, numels):
+    if len(numels) == 4 and bits == 3:
+        from openfl_amd.codec import EdenPlan
+        assert EdenPlan(numels, 3).planes_nbytes[1] == 786_435
+    _check_batch_equals_single(numels, bits)
+
+
+def _check_batch_equals_single(numels, bits):
     from openfl_amd.codec import EdenPlan
-    numels = [5, 1000, 4096, 70_000, 1 << 20, 3]
     rng = np.random.default_rng(11)
     xs = [rng.standard_normal(n).astype(np.float32) for n in numels]
-    seeds = [11, 22, 33, 44, 55, 66]
-    plan = EdenPlan(numels, 8)
+    seeds = [11, 22, 33, 44, 55, 66][:len(numels)]
+    plan = EdenPlan(numels, bits)
     arena = torch.zeros(plan.arena_numel, device=DEV)
     for x, off in zip(xs, plan.elem_offsets):
         arena[off:off + x.size] = torch.from_numpy(x).to(DEV)
-    c = _codec(8)
+    c = _codec(bits)
     sd = torch.tensor(seeds, dtype=torch.int32, device=DEV)
     planes, scales = c.encode_arena(plan, arena, sd)
     y = c.decode_arena(plan, planes, scales, sd)
     torch.cuda.synchronize()
     planes, scales, y = planes.cpu().numpy(), scales.cpu().numpy(), y.cpu().numpy()
     for t, (x, s) in enumerate(zip(xs, seeds)):
-        p1, s1, d1 = gpu_encode(x, s, 8)
+        p1, s1, d1 = gpu_encode(x, s, bits)
         po, pb = plan.planes_offsets[t], plan.planes_nbytes[t]
         np.testing.assert_array_equal(planes[po:po + pb], p1)
         fs = plan.first_slice[t]
         np.testing.assert_array_equal(scales[fs:fs + len(d1)], s1)
-        y1 = gpu_decode(p1, x.size, s1, d1, s, 8)
+        y1 = gpu_decode(p1, x.size, s1, d1, s, bits)
         off = plan.elem_offsets[t]
         np.testing.assert_array_equal(y[off:off + x.size], y1)
 
@@ -623,6 +652,24 @@ def test_row2_variants_bit_identical():
     for row2, pair, wave in ((0, 0, 4096), (1, 0, 4096), (1, 1, 4096), (1, 1, 2), (-1, -1, 2), (-1, -1, 64),
                              (-1, 0, 64)):
         plan = EdenPlan(numels, 8, wave_mib=wave, streams=1, row2=row2, pair=pair)
+        for enc in (True, False):  # the plan runs what its setting says
+            rows = [l for l in plan.launches(enc) if "_row" in l["name"]]
+            sub = [l for l in rows if l["expl"]]
+            signs = [l for l in sub if ("_rowA2" in l["name"] if enc else "_rowC2" in l["name"])]
+            if wave == 64:  # the 2^26 slice in sub-waves, paired unless pair = 0
+                assert len(sub) == 8 and len(signs) == 4
+                assert all(l["paired"] == (pair != 0) for l in signs)
+                assert not any(l["paired"] for l in sub if l not in signs)
+            else:
+                assert not sub
+            if pair == 0 or row2 == 0:
+                assert not any(l["paired"] for l in rows)
+            if row2 == 0:
+                assert not any(n in l["name"] for l in rows for n in ("_rowA2", "k_dec_rowC2"))
+            if row2 == 1:
+                assert not any(l["name"].endswith(("_rowA", "_rowC")) for l in rows)
+            if (row2, pair) == (1, 1):
+                assert any(l["paired"] for l in rows)
         x = torch.empty(plan.arena_numel, device=DEV).normal_(0, 0.01, generator=g.manual_seed(21))
         base = torch.empty(plan.arena_numel, device=DEV).normal_(0, 1.0, generator=g.manual_seed(22))
         seeds = torch.tensor([5, 6, 7, 8, 9, 10, 11, 12], dtype=torch.int32, device=DEV)

@@ -299,3 +299,128 @@ def test_big_slice_sub_waves():
     assert min(i for i, (n, _) in enumerate(split) if n.startswith("ofl::k_enc_rowC2")) > mid[0]
     whole = [n for n, _ in [(l["name"], l["blocks"]) for l in EdenPlan([1 << 26], 8, wave_mib=4096, streams=1).launches(True)]]
     assert whole.count("ofl::k_col<5, false>") == 2 and "ofl::k_enc_rowA2" not in whole
+
+
+def _rows(plan, enc):
+    return [l for l in plan.launches(enc) if "_row" in l["name"]]
+
+
+def test_split_slice_honours_row2_and_pair():
+    """ofl_eden_plan_set_row2 / _set_pair rebuild the schedule: for one 2^26
+    slice at 64 MiB waves, row2 = 0 gives whole-slice passes (no explicit-tile
+    launch), pair = 0 split sub-waves whose D1-applying row launches (encode
+    pass A, decode pass C) walk the unpaired table, pair = 1 / auto the paired
+    one.  Explicit-tile row launches are named after the two-blocks-per-CU
+    kernels, which is what runs them."""
+    from openfl_amd.codec import EdenPlan
+
+    def plan(**kw):
+        return EdenPlan([1 << 26], 8, wave_mib=64, streams=1, **kw)
+
+    for enc in (True, False):
+        d = "enc" if enc else "dec"
+        signs = f"ofl::k_{d}_rowA2" if enc else "ofl::k_dec_rowC2"
+        # row2 = 0: whole-slice persistent passes
+        L = plan(row2=0).launches(enc)
+        assert not any(l["expl"] or l["paired"] for l in L)
+        rows = _rows(plan(row2=0), enc)
+        assert [l["blocks"] for l in rows] == [2048, 2048]
+        assert rows[0]["name"] == f"ofl::k_{d}_rowA" and rows[0]["grid"] == 256
+        if enc:  # encode pass C has its two-blocks-per-CU kernel whatever row2 says
+            assert rows[1]["name"].startswith("ofl::k_enc_rowC2<") and rows[1]["grid"] == 512
+        else:
+            assert rows[1]["name"] == "ofl::k_dec_rowC" and rows[1]["grid"] == 256
+        assert [l["name"] for l in L if "col" in l["name"]] == ["ofl::k_col<5, false>", "ofl::k_col<6, true>",
+                                                                  "ofl::k_col<5, false>"]
+        # pair = 0: split, every row launch over an unpaired explicit list
+        rows = _rows(plan(pair=0), enc)
+        assert len(rows) == 8 and all(l["expl"] and not l["paired"] for l in rows)
+        assert all(l["grid"] == l["blocks"] == 512 for l in rows)
+        assert sum(l["name"] == signs for l in rows) == 4
+        # pair = 1 and auto: the D1-applying sub-wave launches walk the paired table
+        for kw in ({"pair": 1}, {"pair": -1}, {}):
+            rows = _rows(plan(**kw), enc)
+            assert len(rows) == 8 and all(l["expl"] for l in rows)
+            assert [l["paired"] for l in rows] == [l["name"] == signs for l in rows]
+            assert sum(l["paired"] for l in rows) == 4
+            assert all(l["grid"] == (256 if l["paired"] else 512) for l in rows)
+        # explicit-tile row launches are named after the two-blocks-per-CU kernels
+        names = {l["name"].split("<")[0] for l in _rows(plan(), enc)}
+        assert names == {f"ofl::k_{d}_rowA2", f"ofl::k_{d}_rowC2"}
+        # the column launches of the sub-waves are explicit too, never paired
+        cols = [l for l in plan().launches(enc) if "col" in l["name"]]
+        assert sum(l["expl"] for l in cols) == 8 and not any(l["paired"] for l in cols)
+
+
+def test_set_row2_and_pair_rebuild_the_schedule():
+    """Called on a plan that already has its schedule (as EdenPlan.__init__
+    does, after set_schedule), the two setters rebuild it: the launch list
+    changes with each call.  (Their rejection after the first encode needs a
+    GPU: tests/test_gpu_eden_variants.py.)"""
+    from openfl_amd import _lib
+    from openfl_amd.codec import EdenPlan
+    L = _lib.lib()
+    p = EdenPlan([1 << 26], 8, wave_mib=64, streams=1)
+    assert all(l["expl"] for l in _rows(p, True)) and any(l["paired"] for l in _rows(p, True))
+    assert L.ofl_eden_plan_set_pair(p.handle, 0) == _lib.OFL_OK
+    assert all(l["expl"] and not l["paired"] for l in _rows(p, True) + _rows(p, False))
+    assert L.ofl_eden_plan_set_row2(p.handle, 0) == _lib.OFL_OK
+    assert not any(l["expl"] for l in p.launches(True) + p.launches(False))
+    assert L.ofl_eden_plan_set_row2(p.handle, -1) == _lib.OFL_OK
+    assert L.ofl_eden_plan_set_pair(p.handle, 1) == _lib.OFL_OK
+    assert sum(l["paired"] for l in _rows(p, True)) == 4 and sum(l["paired"] for l in _rows(p, False)) == 4
+    assert L.ofl_eden_plan_set_row2(p.handle, 2) == _lib.OFL_EINVAL
+    assert L.ofl_eden_plan_set_pair(p.handle, -2) == _lib.OFL_EINVAL
+    assert L.ofl_eden_plan_launch_detail(p.handle, 1, 10 ** 6, None, None, None) == _lib.OFL_EINVAL
+    assert L.ofl_eden_plan_launch_detail(p.handle, 1, 0, None, None, None) == _lib.OFL_OK
+
+
+def test_nt_middle_pass_is_named():
+    """The whole-slice middle pass of a split 2^28 slice streams its
+    intermediate (k_col6<7, true, 15, true>): the default plan names exactly
+    one per direction, and no launch under the plain middle pass's name."""
+    from openfl_amd.codec import EdenPlan
+    p = EdenPlan([1 << 28], 8)
+    for enc in (True, False):
+        names = [l["name"] for l in p.launches(enc)]
+        assert names.count("ofl::k_col6<7, true, 15, true>") == 1
+        assert "ofl::k_col6<7, true, 15>" not in names
+
+
+def test_variant_configs_cover_every_row_kernel():
+    """Coverage ledger of tests/test_gpu_eden_variants.py: over the plans of
+    VARIANT_CONFIGS, every row kernel runs in every way the public setters can
+    reach it -- (direction, kernel, explicit tile list, paired table)."""
+    from tests import eden_variants as V
+    reached = set()
+    for cfg in V.VARIANT_CONFIGS:
+        plan = V.make_plan(cfg)
+        rows = V.row_launches(plan)
+        expl, paired = V.expected_shape(cfg)
+        for d in ("enc", "dec"):
+            assert any(r[2] for r in rows if r[0] == d) == expl, (cfg, d)
+            assert any(r[3] for r in rows if r[0] == d) == paired, (cfg, d)
+        reached |= rows
+    wanted = {
+        ("enc", "k_enc_rowA", False, False),
+        ("enc", "k_enc_rowA2", False, False), ("enc", "k_enc_rowA2", False, True),
+        ("enc", "k_enc_rowA2", True, False), ("enc", "k_enc_rowA2", True, True),
+        ("dec", "k_dec_rowA", False, False),
+        ("dec", "k_dec_rowA2", False, False), ("dec", "k_dec_rowA2", True, False),
+        ("dec", "k_dec_rowC", False, False),
+        ("dec", "k_dec_rowC2", False, False), ("dec", "k_dec_rowC2", False, True),
+        ("dec", "k_dec_rowC2", True, False), ("dec", "k_dec_rowC2", True, True),
+        ("enc", "k_enc_rowC2", False, False), ("enc", "k_enc_rowC2", True, False),
+    }
+    assert wanted <= reached, sorted(wanted - reached)
+    # Not reachable from the public setters, so in no config:
+    #  * k_enc_rowC (the persistent encode pass C): only the process-wide
+    #    OFL_EDEN_ROWC2=0 selects it, and the environment knobs are read once
+    #    per process;
+    #  * paired k_dec_rowA2 / k_enc_rowC2: these passes apply no D1 signs, and
+    #    only the sign-applying passes have a paired table.
+    unreachable = {("enc", "k_enc_rowC", False, False), ("dec", "k_dec_rowA2", False, True),
+                   ("dec", "k_dec_rowA2", True, True), ("enc", "k_enc_rowC2", False, True),
+                   ("enc", "k_enc_rowC2", True, True)}
+    assert not (unreachable & reached)
+    assert reached == wanted
