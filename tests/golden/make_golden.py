@@ -23,8 +23,10 @@ Reference functions exercised (citations are /root/reference-relative):
   openfl/pipelines/random_shift_pipeline.py:12-77  RandomShiftTransformer / Pipeline
   openfl/pipelines/no_compression_pipeline.py:10-15 NoCompressionPipeline
 
-Usage:  python tests/golden/make_golden.py [--only plain]
-        (writes tests/golden/*.npz, *.json; --only plain rewrites plain_golden.json only)
+Usage:  python tests/golden/make_golden.py [--only plain | --only designed]
+        (writes tests/golden/*.npz, *.json; --only plain rewrites plain_golden.json only,
+        --only designed writes eden_designed.json only: the reference's planes hashes and
+        scales on the designed inputs of tests/eden_exact.py)
 """
 import hashlib
 import importlib
@@ -284,11 +286,39 @@ def plain_fixtures(ref):
     return out
 
 
+def designed_fixtures(ref):
+    """The reference's Eden.compress on the designed inputs of tests/eden_exact.py
+    (bins chosen first, x the inverse rotation of alpha * C[bins]): per case the
+    sha256 of its planes and its scales.  Data only; the inputs are rebuilt by
+    the tests from the seeds recorded here."""
+    import torch
+    torch.set_num_threads(1)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from tests import eden_exact as X
+    cases = []
+    for dims in X.FIXTURE_DIMS:
+        for b in range(1, 9):
+            x, _, alphas = X.designed(dims, b)
+            planes, scales, rdims, total = ref["eden_pipeline"].Eden(nbits=b).compress(x.numpy(), X.SEED)
+            planes = np.asarray(planes, dtype=np.uint8)
+            assert [int(d) for d in rdims] == dims and int(total) == sum(dims)
+            cases.append({"dims": dims, "bits": b, "seed": X.SEED, "rng_seed": [X.SEED, b] + dims,
+                          "alphas": alphas, "planes_len": int(planes.size), "planes_sha256": sha(planes),
+                          "scales": [float(s) for s in scales]})
+    return {"cases": cases}
+
+
 def main():
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
     ref = _load_reference()
+    if only == "designed":
+        with open(os.path.join(OUT, "eden_designed.json"), "w") as f:
+            json.dump(designed_fixtures(ref), f, indent=1)
+        print("wrote eden_designed.json")
+        return
     with open(os.path.join(OUT, "plain_golden.json"), "w") as f:
         json.dump(plain_fixtures(ref), f, indent=1)
-    if "--only" in sys.argv and sys.argv[sys.argv.index("--only") + 1] == "plain":
+    if only == "plain":
         print("wrote plain_golden.json")
         return
     arrays, index = eden_fixtures(ref)

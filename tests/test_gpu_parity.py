@@ -255,7 +255,10 @@ def test_large_slice_property_2p29():
     """Llama-3-8B embed/lm_head size (one 2^29 slice, 128256 x 4096 elements):
     too big for the oracle in test time, so check size-independent properties:
     8-bit Eden error ~6.4e-3 relative (Gaussian input), decode deterministic,
-    linearity of the scale, every plane byte written."""
+    linearity of the scale, every plane byte written.  The encode's ground
+    truth at this size is tests/test_gpu_eden_exact.py::
+    test_designed_exact_five_pass[29-8]: a designed 2^29 input whose planes
+    and scale are known exactly, built and compared on the device."""
     n = 128256 * 4096
     g = torch.Generator(device=DEV).manual_seed(5)
     x = torch.empty(n, device=DEV).normal_(0, 0.01, generator=g)
