@@ -429,6 +429,70 @@ int ofl_apply_delta_ranges(const float* base, const float* delta, float* out, in
 int ofl_wavg_delta32_ranges(int ncollab, const float* const* xs, const double* weights, double wsum,
                             const float* base, int nranges, const int64_t* starts, const int64_t* dst, int64_t total,
                             float* delta32_out, void* stream);
+/* The robust aggregators a plan can name in aggregation_type, on the same
+ * arenas.
+ *
+ * ofl_median_delta  Median (median.py:48-49): np.median(stack, axis=0) of
+ *                 ncollab float32 arenas, by value: the middle order statistic
+ *                 for odd ncollab, (lo + hi) / 2 in float32 for even (3e38,
+ *                 3e38 -> inf), NaN where a column holds a NaN; tied -0.0 and
+ *                 +0.0 may come out with either sign.  xs: host array of
+ *                 1 <= ncollab <= 128 device pointers (<= 16: a register
+ *                 sorting network, above: a per-thread LDS column; more ->
+ *                 OFL_EINVAL).  Outputs (device, either may be NULL):
+ *                 median_out float32, delta_out = median - base as a float32
+ *                 subtract (generate_delta of two float32 arrays; base NULL:
+ *                 the median).  Async.
+ * ofl_gmedian_delta  GeometricMedian (geometric_median.py:27-56): Weiszfeld's
+ *                 algorithm as the reference runs it, separately for every
+ *                 tensor of the arena, all in float64 and without a host round
+ *                 trip.  w0: host [ncollab], the weights already divided by
+ *                 their sum.  The median is (sum_c x_c W_c) / sum(W) as
+ *                 np.average forms it; obj0 from the first average, then up to
+ *                 maxiter rounds of W <- W / max(eps, dist), renormalised, the
+ *                 new average, the objective with the NEW weights, and the
+ *                 test |prev - obj| < ftol * obj (strict, so obj == 0 never
+ *                 stops).  Distances are summed per chunk by one block and
+ *                 the chunks in order: no atomics, the same bits on every run;
+ *                 the order differs from NumPy's, so the result agrees with
+ *                 the reference to summation rounding, not bit for bit.
+ *                 chunks_dev: DEVICE table of nchunks records that tile every
+ *                 tensor in order (length <= 4096, never spanning two
+ *                 tensors); tensor_chunk0_dev: DEVICE [ntensors + 1] first
+ *                 chunk of every tensor.  1 <= ncollab <= 16 (more ->
+ *                 OFL_EINVAL; chaining is not offered).  Outputs (device, any
+ *                 may be NULL): agg_out float64, delta64_out / delta32_out as
+ *                 ofl_wavg_delta writes them, iters_out [ntensors] rounds run.
+ *                 Elements outside every chunk are not written.  ws: device,
+ *                 ofl_gmedian_workspace_bytes().  Async.
+ * ofl_agg_delta_seeds  ofl_wavg_delta_seeds for an aggregate arena that is
+ *                 already computed (every pointer DEVICE memory, tables as
+ *                 there).  agg_is_f64 != 0: float64 aggregate, delta = agg -
+ *                 (double)base, float64 sums and seed arithmetic as there
+ *                 (packed_dev: total doubles).  agg_is_f64 == 0: float32
+ *                 aggregate, the delta is a float32 subtract, the serial sum a
+ *                 left-to-right float32 chain and sum * 13 + 7 two float32
+ *                 roundings, widened only for the hash (packed_dev: total
+ *                 floats; sums_dev receives the float32 sums widened).  That
+ *                 is what the seed formula gives for a float32 array under
+ *                 NumPy >= 2 scalar promotion (NEP 50: np.float32 * 13 stays
+ *                 float32); NumPy 1.x would widen there.  base may be NULL.
+ *                 Async. */
+typedef struct {
+    int64_t start;   /* arena element offset */
+    int32_t len;     /* 1..4096 */
+    int32_t tensor;
+} ofl_gm_chunk;
+int ofl_median_delta(int ncollab, const float* const* xs, const float* base, int64_t n, float* median_out,
+                     float* delta_out, void* stream);
+size_t ofl_gmedian_workspace_bytes(int ntensors, int nchunks);
+int ofl_gmedian_delta(int ncollab, const float* const* xs, const double* w0, int maxiter, double eps, double ftol,
+                      const float* base, int ntensors, const ofl_gm_chunk* chunks_dev, int nchunks,
+                      const int32_t* tensor_chunk0_dev, double* agg_out, double* delta64_out, float* delta32_out,
+                      int32_t* iters_out, void* ws, size_t ws_bytes, void* stream);
+int ofl_agg_delta_seeds(const void* agg_dev, int agg_is_f64, const float* base, int nranges, const int64_t* starts_dev,
+                        const int64_t* dst_dev, int64_t total, const int64_t* draws_dev, uint32_t* seeds_dev,
+                        double* sums_dev, void* packed_dev, void* stream);
 
 /* ---- gzip of rank arrays (csrc/deflate_kernels.hip) -------------------------
  * GZIPTransformer.forward (kc_pipeline.py:128-141, skc_pipeline.py:201-215,

@@ -35,6 +35,7 @@ EXPORTS = (
     "ofl_py_hash_doubles",
     "ofl_wavg_points_workspace_bytes", "ofl_wavg_delta_points", "ofl_apply_delta",
     "ofl_apply_delta_ranges", "ofl_wavg_delta32_ranges", "ofl_sub_f32_f64",
+    "ofl_median_delta", "ofl_gmedian_workspace_bytes", "ofl_gmedian_delta", "ofl_agg_delta_seeds",
     "ofl_gzip_last_error", "ofl_gzip_ranks_workspace_bytes", "ofl_gzip_ranks_bound", "ofl_gzip_ranks", "ofl_gzip_ranks_to", "ofl_gzip_label_to", "ofl_side_stream",
     "ofl_gunzip_members", "ofl_gzip_member_index", "ofl_inflate_members", "ofl_inflate_tlz_workspace_bytes",
     "ofl_inflate_tlz", "ofl_inflate_tlz_async", "ofl_inflate_tlz_wait", "ofl_inflate_tlz_launch", "ofl_inflate_tlz_launch_lut", "ofl_inflate_tlz_check", "ofl_gzip_profile", "ofl_gzip_profile_collect",
@@ -177,6 +178,15 @@ def _bind(L):
     L.ofl_apply_delta_ranges.restype = i32
     L.ofl_wavg_delta32_ranges.argtypes = [i32, vp, vp, ctypes.c_double, vp, i32, vp, vp, i64, vp, vp]
     L.ofl_wavg_delta32_ranges.restype = i32
+    L.ofl_median_delta.argtypes = [i32, vp, vp, i64, vp, vp, vp]
+    L.ofl_median_delta.restype = i32
+    L.ofl_gmedian_workspace_bytes.argtypes = [i32, i32]
+    L.ofl_gmedian_workspace_bytes.restype = sz
+    L.ofl_gmedian_delta.argtypes = [i32, vp, vp, i32, ctypes.c_double, ctypes.c_double, vp, i32, vp, i32, vp, vp, vp,
+                                    vp, vp, vp, sz, vp]
+    L.ofl_gmedian_delta.restype = i32
+    L.ofl_agg_delta_seeds.argtypes = [vp, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.ofl_agg_delta_seeds.restype = i32
     L.ofl_gzip_last_error.restype = ctypes.c_char_p
     L.ofl_gzip_ranks_workspace_bytes.argtypes = [i64]
     L.ofl_gzip_ranks_workspace_bytes.restype = sz

@@ -128,6 +128,155 @@ class WeightedAverage:
         return self.call(local_tensors, *args)
 
 
+_MEDIAN_MAX_C = 128   # ofl_median_delta: <= 16 in registers, <= 128 through LDS
+_GMEDIAN_MAX_C = 16   # ofl_gmedian_delta: one launch's collaborators, no chaining
+_GM_CHUNK = 4096
+_GM_CHUNK_DT = np.dtype([("start", "<i8"), ("len", "<i4"), ("tensor", "<i4")])  # ofl_gm_chunk
+AGGREGATIONS = ("weighted_average", "median", "geometric_median")
+
+
+def _f32_stack(name, tensors):
+    arrs = [np.asarray(t) for t in tensors]
+    if not arrs:
+        raise _lib.CodecError(f"{name}: no tensors")
+    shape = arrs[0].shape
+    if any(a.shape != shape or a.dtype != np.float32 for a in arrs):
+        raise _lib.CodecError(f"{name}: float32 tensors of one shape")
+    return arrs, shape, int(np.prod(shape, dtype=np.int64))
+
+
+def _check_collaborators(name, n, limit):
+    if n > limit:
+        raise _lib.CodecError(f"{name}: {n} collaborators, at most {limit} are supported")
+
+
+def _median_launch(xs, base, n, med=None, delta=None, device=None):
+    _check_collaborators("median", len(xs), _MEDIAN_MAX_C)
+    ptrs = np.asarray([x.data_ptr() for x in xs], np.uint64)
+    _lib.check_agg(_lib.lib().ofl_median_delta(
+        len(xs), ptrs.ctypes.data, base.data_ptr() if base is not None else None, int(n),
+        med.data_ptr() if med is not None else None, delta.data_ptr() if delta is not None else None,
+        _stream(device)))
+
+
+def median(tensors, device=None):
+    """np.median(tensors, axis=0) on the GPU (median.py:48-49): float32
+    tensors, float32 result, equal by value (tied zeros may differ in sign);
+    at most 128 tensors."""
+    dev = resolve_device(device)
+    arrs, shape, n = _f32_stack("median", tensors)
+    _check_collaborators("median", len(arrs), _MEDIAN_MAX_C)
+    with torch.cuda.device(dev):
+        out = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        if n:
+            xs = [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev) for a in arrs]
+            _median_launch(xs, None, n, med=out, device=dev)
+        return out[:n].cpu().numpy().reshape(shape)
+
+
+class Median:
+    """AggregationFunction plugin (median.py:12-49): call(local_tensors, ...) ->
+    np.median of the LocalTensor tensors on the GPU; the weights are ignored,
+    as in the reference."""
+
+    def __init__(self, device=None):
+        self.device = device
+
+    def call(self, local_tensors, *_):
+        return median([x.tensor for x in local_tensors], self.device)
+
+    def __call__(self, local_tensors, *args):
+        return self.call(local_tensors, *args)
+
+
+def _gm_start_weights(weights, n):
+    """geometric_median.py:41: np.asarray(weights) / sum(weights)."""
+    _f64_weights(weights, n)
+    w = np.asarray(weights)
+    tot = sum(w)
+    if tot == 0:
+        raise ZeroDivisionError("Weights sum to zero, can't be normalized")
+    return np.ascontiguousarray(w / tot, np.float64)
+
+
+def _gm_chunk_table(offsets, numels):
+    """ofl_gmedian_delta's chunk table: every tensor tiled in order by chunks of
+    <= 4096 elements -> (records, first chunk of every tensor [T + 1])."""
+    parts, first = [], [0]
+    for t, (o, n) in enumerate(zip(offsets, numels)):
+        k = (n + _GM_CHUNK - 1) // _GM_CHUNK
+        at = _GM_CHUNK * np.arange(k, dtype=np.int64)
+        c = np.zeros(k, _GM_CHUNK_DT)
+        c["start"] = o + at
+        c["len"] = np.minimum(_GM_CHUNK, n - at)
+        c["tensor"] = t
+        parts.append(c)
+        first.append(first[-1] + k)
+    return np.concatenate(parts) if parts else np.zeros(0, _GM_CHUNK_DT), np.asarray(first, np.int32)
+
+
+class _GmLayout:
+    """Device tables and workspace of ofl_gmedian_delta for one arena layout."""
+
+    def __init__(self, offsets, numels, device):
+        chunks, first = _gm_chunk_table(offsets, numels)
+        self.ntensors = len(numels)
+        self.nchunks = int(chunks.size)
+        raw = np.frombuffer(chunks.tobytes() or bytes(_GM_CHUNK_DT.itemsize), np.uint8).copy()
+        self.chunks = torch.from_numpy(raw).to(device)
+        self.first = torch.from_numpy(first).to(device)
+        self.iters = torch.zeros(max(self.ntensors, 1), dtype=torch.int32, device=device)
+        need = int(_lib.lib().ofl_gmedian_workspace_bytes(self.ntensors, self.nchunks))
+        self.ws = torch.empty(need, dtype=torch.uint8, device=device)
+
+    def launch(self, xs, w0, maxiter, eps, ftol, base, agg=None, delta64=None, delta32=None, device=None):
+        _check_collaborators("geometric_median", len(xs), _GMEDIAN_MAX_C)
+        ptrs = np.asarray([x.data_ptr() for x in xs], np.uint64)
+        _lib.check_agg(_lib.lib().ofl_gmedian_delta(
+            len(xs), ptrs.ctypes.data, w0.ctypes.data, int(maxiter), float(eps), float(ftol),
+            base.data_ptr() if base is not None else None, self.ntensors, self.chunks.data_ptr(), self.nchunks,
+            self.first.data_ptr(), agg.data_ptr() if agg is not None else None,
+            delta64.data_ptr() if delta64 is not None else None, delta32.data_ptr() if delta32 is not None else None,
+            self.iters.data_ptr(), self.ws.data_ptr(), self.ws.numel(), _stream(device)))
+
+
+def geometric_median(tensors, weights, maxiter=4, eps=1e-5, ftol=1e-6, device=None, return_iterations=False):
+    """geometric_median(tensors, weights, maxiter, eps, ftol) of
+    geometric_median.py:27-56 on the GPU: Weiszfeld's algorithm in float64 with
+    the reference's sequence of passes and its break test.  float32 tensors
+    (at most 16), float64 result; the distance sums run in another order than
+    NumPy's, so the result agrees to summation rounding.  return_iterations:
+    also the number of Weiszfeld rounds run."""
+    dev = resolve_device(device)
+    arrs, shape, n = _f32_stack("geometric_median", tensors)
+    _check_collaborators("geometric_median", len(arrs), _GMEDIAN_MAX_C)
+    w0 = _gm_start_weights(weights, len(arrs))
+    with torch.cuda.device(dev):
+        lay = _GmLayout([0], [n], dev)
+        xs = [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev) if n else
+              torch.zeros(1, dtype=torch.float32, device=dev) for a in arrs]
+        agg = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        lay.launch(xs, w0, maxiter, eps, ftol, None, agg=agg, device=dev)
+        res = agg[:n].cpu().numpy().reshape(shape)
+        return (res, int(lay.iters[0].item())) if return_iterations else res
+
+
+class GeometricMedian:
+    """AggregationFunction plugin (geometric_median.py:76-112): call(local_tensors,
+    ...) -> geometric_median of the LocalTensor tensors by their weights, on the
+    GPU (the reference's defaults: maxiter 4, eps 1e-5, ftol 1e-6)."""
+
+    def __init__(self, device=None):
+        self.device = device
+
+    def call(self, local_tensors, *_):
+        tensors, weights = zip(*[(x.tensor, x.weight) for x in local_tensors])
+        return geometric_median(tensors, np.array(weights), device=self.device)
+
+    def __call__(self, local_tensors, *args):
+        return self.call(local_tensors, *args)
+
+
 class RoundEnd:
     """Aggregator._prepare_trained for a whole model update (aggregator.py:780-865).
 
@@ -139,9 +288,19 @@ class RoundEnd:
     large slices' first encode pass computes the delta from the collaborator
     arenas itself (ofl_eden_encode_wavg) instead of reading a delta arena
     the averaging kernel wrote -- same bytes, 8 B/element less HBM traffic.
+    aggregation: "weighted_average" (default), "median" (np.median per
+    element, at most 128 collaborators, run()'s weights may be None and its
+    agg_out is float32) or "geometric_median" (Weiszfeld per tensor with the
+    reference's defaults, at most 16 collaborators, agg_out float64).  The two
+    robust aggregators write the delta arena with their own kernels, take the
+    seeds from it (ofl_agg_delta_seeds) and are never fused; everything after
+    the seeds is the same code.
     """
 
-    def __init__(self, pipeline, shapes, device=None, fused=True):
+    def __init__(self, pipeline, shapes, device=None, fused=True, aggregation="weighted_average"):
+        if aggregation not in AGGREGATIONS:
+            raise _lib.CodecError(f"aggregation must be one of {AGGREGATIONS}, not {aggregation!r}")
+        self.aggregation = aggregation
         tr = pipeline.transformers[0]
         self.transformer = tr
         self.device = resolve_device(device) if device is not None else tr.eden.device
@@ -191,7 +350,7 @@ class RoundEnd:
         # pass computes the delta from the collaborators' arenas itself, so the
         # delta arena is written only where something else reads it -- the
         # tensors the codec does not touch and the slices of <= 2^15 elements
-        self.fused = bool(fused) and self.plan is not None
+        self.fused = bool(fused) and self.plan is not None and aggregation == "weighted_average"
         fz = [(self.offsets[i], self.numels[i]) for i in rest]
         for t, i in enumerate(self.big):
             _, lens = slice_plan(self.numels[i])
@@ -208,6 +367,10 @@ class RoundEnd:
         self._host_args = None   # pinned [collaborator pointers | weights | draws], reused after _args_done
         self._dev_args = None
         self._args_done = None
+        # geometric median: the chunk table of this layout, per-tensor state and
+        # (without agg_out) the float64 aggregate the delta and seeds come from
+        self._gm = _GmLayout(self.offsets, self.numels, self.device) if aggregation == "geometric_median" else None
+        self._gm_agg = None
 
     # -- arenas --
     def arena(self):
@@ -239,7 +402,10 @@ class RoundEnd:
         layout); weights: per collaborator; base_arena: the previous model
         (None: no base, the delta is the average).  Writes the new model
         into `out` (default: a new arena; may be base_arena) and, if given,
-        the float64 average into agg_out (arena_numel elements).
+        the float64 average into agg_out (arena_numel elements).  With
+        aggregation "median" the weights are ignored (may be None) and agg_out
+        is float32; with "geometric_median" agg_out is float64 and is written
+        inside the tensors only.
         -> (new model arena, [(payload bytes, [metadata])] per tensor or None,
         seeds: a list with payloads, else the device int32 tensor -- without
         payloads nothing synchronises with the host)."""
@@ -248,8 +414,11 @@ class RoundEnd:
         for x in xs + ([base_arena] if base_arena is not None else []):
             if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= self.arena_numel):
                 raise _lib.CodecError("arenas must be contiguous float32 device tensors of arena_numel elements")
-        if agg_out is not None and not (agg_out.dtype == torch.float64 and agg_out.numel() >= self.arena_numel):
-            raise _lib.CodecError("agg_out must be float64 with arena_numel elements")
+        agg_dtype = torch.float32 if self.aggregation == "median" else torch.float64
+        if agg_out is not None and not (agg_out.dtype == agg_dtype and agg_out.numel() >= self.arena_numel):
+            raise _lib.CodecError(f"agg_out must be {str(agg_dtype)[6:]} with arena_numel elements")
+        if self.aggregation != "weighted_average":
+            return self._run_robust(xs, weights, base_arena, agg_out, payloads, out)
         w64 = _f64_weights(weights, len(xs))
         wsum = self._wsum(w64)
         L = _lib.lib()
@@ -277,24 +446,76 @@ class RoundEnd:
             T = len(self.numels)
             C = len(xs)
             draws = np.random.randint(1, 2 ** 16, size=T).astype(np.int64) if T else np.zeros(0, np.int64)
-            need = 2 * C + max(T, 1)
-            if self._host_args is None or self._host_args.numel() < need:
-                self._host_args = torch.empty(need, dtype=torch.int64).pin_memory()
-                self._dev_args = torch.empty(need, dtype=torch.int64, device=dev)
-                self._args_done = torch.cuda.Event()
-            else:
-                self._args_done.synchronize()  # the previous call's copy has left the pinned buffer
-            ha = self._host_args.numpy()
-            ha[:C] = np.asarray([x.data_ptr() for x in xs], np.uint64).view(np.int64)
-            ha[C:2 * C] = w64.view(np.int64)
-            ha[2 * C:2 * C + T] = draws
-            self._dev_args[:need].copy_(self._host_args[:need], non_blocking=True)
-            self._args_done.record()
-            dp = self._dev_args.data_ptr()
+            dp = self._stage_args([np.asarray([x.data_ptr() for x in xs], np.uint64).view(np.int64),
+                                   w64.view(np.int64), draws])
             _lib.check_agg(L.ofl_wavg_delta_seeds(
                 C, dp, dp + 8 * C, wsum, base_arena.data_ptr() if base_arena is not None else None, T,
                 self._seed_start.data_ptr(), self._seed_dst.data_ptr(), self._seed_single.data_ptr(), self._seed_total,
                 dp + 16 * C, self._seeds.data_ptr(), self._seed_sums.data_ptr(), self._packed.data_ptr(), _stream(dev)))
+            return self._encode_apply(delta, base_arena, payloads, out, (dp, C, wsum) if fused else None)
+
+    def _stage_args(self, parts):
+        """int64 words (pointers, weight bits, draws) -> the device copy's
+        address, through a pinned buffer that is reused once its copy has left."""
+        dev = self.device
+        need = sum(len(p) for p in parts) + 1
+        if self._host_args is None or self._host_args.numel() < need:
+            self._host_args = torch.empty(need, dtype=torch.int64).pin_memory()
+            self._dev_args = torch.empty(need, dtype=torch.int64, device=dev)
+            self._args_done = torch.cuda.Event()
+        else:
+            self._args_done.synchronize()  # the previous call's copy has left the pinned buffer
+        ha = self._host_args.numpy()
+        o = 0
+        for p in parts:
+            ha[o:o + len(p)] = p
+            o += len(p)
+        self._dev_args[:need].copy_(self._host_args[:need], non_blocking=True)
+        self._args_done.record()
+        return self._dev_args.data_ptr()
+
+    def _run_robust(self, xs, weights, base_arena, agg_out, payloads, out):
+        """run() for "median" and "geometric_median": the delta arena from
+        their kernels, the seeds from that delta, then the shared tail."""
+        dev = self.device
+        L = _lib.lib()
+        T = len(self.numels)
+        with torch.cuda.device(dev):
+            delta = torch.empty(self.arena_numel, dtype=torch.float32, device=dev)
+            if self.aggregation == "median":
+                # elementwise over the whole arena; the float32 delta it writes
+                # is the array the seed formula sums
+                _median_launch(xs, base_arena, self.arena_numel, med=agg_out, delta=delta, device=dev)
+                src, is_f64, seed_base = delta, 0, None
+            else:
+                _check_collaborators("geometric_median", len(xs), _GMEDIAN_MAX_C)
+                w0 = _gm_start_weights(weights, len(xs))
+                if agg_out is None:
+                    if self._gm_agg is None:
+                        self._gm_agg = torch.zeros(self.arena_numel, dtype=torch.float64, device=dev)
+                    agg_out = self._gm_agg
+                self._gm.launch(xs, w0, 4, 1e-5, 1e-6, base_arena, agg=agg_out, delta32=delta, device=dev)
+                # generate_delta of the float64 aggregate: agg - base in float64
+                src, is_f64, seed_base = agg_out, 1, base_arena
+            draws = np.random.randint(1, 2 ** 16, size=T).astype(np.int64) if T else np.zeros(0, np.int64)
+            dp = self._stage_args([draws])
+            _lib.check_agg(L.ofl_agg_delta_seeds(
+                src.data_ptr(), is_f64, seed_base.data_ptr() if seed_base is not None else None, T,
+                self._seed_start.data_ptr(), self._seed_dst.data_ptr(), self._seed_total, dp,
+                self._seeds.data_ptr(), self._seed_sums.data_ptr(), self._packed.data_ptr(), _stream(dev)))
+            return self._encode_apply(delta, base_arena, payloads, out, None)
+
+    def _encode_apply(self, delta, base_arena, payloads, out, wavg):
+        """run() from the seeds on: encode, payloads, decode fused with
+        apply_delta, the small tensors' float32 payloads and the gap zeroing.
+        wavg: (device args, collaborators, weight sum) for the fused encode."""
+        dev = self.device
+        L = _lib.lib()
+        T = len(self.numels)
+        fused = wavg is not None
+        if fused:
+            dp, C, wsum = wavg
+        with torch.cuda.device(dev):
             seeds = None
             if payloads:
                 seeds = [int(v) for v in self._seeds[:T].cpu().numpy()]

@@ -25,7 +25,9 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <utility>
 
+#include "median_net.h"
 #include "ofl_codec.h"
 
 namespace agg {
@@ -595,6 +597,518 @@ int ofl_apply_delta_ranges(const float* base, const float* delta, float* out, in
     if (!base || !delta || !out || !starts || !dst) return afail(OFL_EINVAL, "apply_delta_ranges: bad arguments");
     hipLaunchKernelGGL(agg::k_apply_ranges, dim3(grid_for(total, 1)), dim3(agg::kNT), 0,
                        static_cast<hipStream_t>(stream), base, delta, out, starts, dst, nranges);
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+}  // extern "C"
+
+// ---- robust aggregators: Median and GeometricMedian ---------------------------
+// (reference: interface/aggregation_functions/median.py:48-49,
+//  geometric_median.py:27-56)
+
+namespace agg {
+
+constexpr int kMedMaxC = 128;  // the LDS path's column height
+constexpr int kMedLdsNT = 64;  // its block: 128 x 64 floats = 32 KiB of LDS
+
+struct MedArgs {
+    const float* x[kMaxC];
+    const float* base;  // nullable: delta = median when absent
+    float* med;         // nullable
+    float* delta;       // nullable: median - base, a float32 subtract
+    int64_t n;
+};
+struct MedArgsN {
+    const float* x[kMedMaxC];
+    int nc;
+    const float* base;
+    float* med;
+    float* delta;
+    int64_t n;
+};
+
+template <int C>
+__device__ __forceinline__ void med_elem(const MedArgs& a, int64_t i) {
+    float v[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = a.x[c][i];
+    const float m = mednet::median_of<C>(v);
+    if (a.med) a.med[i] = m;
+    if (a.delta) a.delta[i] = a.base ? m - a.base[i] : m;
+}
+
+// 4 consecutive elements per thread, 16-B loads of every collaborator's arena
+// (the kernel reads 4 C + 4 bytes and writes 4 to 8 per element)
+template <int C>
+__device__ __forceinline__ void med_quad(const MedArgs& a, int64_t i) {
+    float4 q[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) q[c] = *reinterpret_cast<const float4*>(a.x[c] + i);
+    float v[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = q[c].x;
+    const float m0 = mednet::median_of<C>(v);
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = q[c].y;
+    const float m1 = mednet::median_of<C>(v);
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = q[c].z;
+    const float m2 = mednet::median_of<C>(v);
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = q[c].w;
+    const float m3 = mednet::median_of<C>(v);
+    if (a.med) *reinterpret_cast<float4*>(a.med + i) = make_float4(m0, m1, m2, m3);
+    if (a.delta) {
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.base) b = *reinterpret_cast<const float4*>(a.base + i);
+        *reinterpret_cast<float4*>(a.delta + i) =
+            a.base ? make_float4(m0 - b.x, m1 - b.y, m2 - b.z, m3 - b.w) : make_float4(m0, m1, m2, m3);
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(kNT) void k_median(MedArgs a, int vec) {
+    const int64_t stride = (int64_t)gridDim.x * kNT;
+    const int64_t t0 = (int64_t)blockIdx.x * kNT + threadIdx.x;
+    int64_t tail = 0;
+    if (vec) {
+        const int64_t n4 = a.n >> 2;
+        for (int64_t q = t0; q < n4; q += stride) med_quad<C>(a, 4 * q);
+        tail = 4 * n4;
+    }
+    for (int64_t i = tail + t0; i < a.n; i += stride) med_elem<C>(a, i);
+}
+
+// 17..128 collaborators: every thread insertion-sorts its column in LDS, laid
+// out [c][thread] so the lanes of a wave hit distinct banks
+__global__ __launch_bounds__(kMedLdsNT) void k_median_lds(MedArgsN a) {
+    __shared__ float col[kMedMaxC][kMedLdsNT];
+    const int tid = threadIdx.x;
+    for (int64_t i = (int64_t)blockIdx.x * kMedLdsNT + tid; i < a.n; i += (int64_t)gridDim.x * kMedLdsNT) {
+        bool nan = false;
+        for (int c = 0; c < a.nc; ++c) {
+            const float x = a.x[c][i];
+            nan |= x != x;
+            int j = c;
+            while (j > 0 && col[j - 1][tid] > x) {
+                col[j][tid] = col[j - 1][tid];
+                --j;
+            }
+            col[j][tid] = x;
+        }
+        float m = col[a.nc / 2][tid];
+        if (!(a.nc & 1)) m = (col[a.nc / 2 - 1][tid] + m) * 0.5f;
+        if (nan) m = NAN;
+        if (a.med) a.med[i] = m;
+        if (a.delta) a.delta[i] = a.base ? m - a.base[i] : m;
+    }
+}
+
+// Weiszfeld's algorithm per tensor of an arena.  State per tensor t (device,
+// float64): the weight row W[t][16], its in-order sum wsum[t] (np.average's
+// denominator), the distances d[t][16], the objective, a done flag and the
+// rounds run.  The current median m = (sum_c x_c W[t][c]) / wsum[t] is formed
+// on the fly wherever it is needed, never stored between passes.
+struct GmArgs {
+    const float* x[kMaxC];
+    int nc;
+    const ofl_gm_chunk* chunks;  // [nchunks] (arena start, length <= 4096, tensor)
+    int nchunks;
+    const int32_t* tchunk0;      // [nt + 1] first chunk of every tensor
+    int nt;
+    double* W;        // [nt][16]
+    double* wsum;     // [nt]
+    double* obj;      // [nt]
+    int32_t* done;    // [nt]
+    int32_t* iters;   // [nt]
+    double* partial;  // [nchunks][16] squared distances of one chunk
+    double eps, ftol;
+    const float* base;
+    double* agg;
+    double* delta64;
+    float* delta32;
+};
+struct GmW0 {
+    double w[kMaxC];
+};
+
+__global__ __launch_bounds__(64) void k_gm_init(GmArgs a, GmW0 w0) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.nt) return;
+    double s = 0.0;
+    for (int c = 0; c < a.nc; ++c) {
+        a.W[t * kMaxC + c] = w0.w[c];
+        s = c ? s + w0.w[c] : w0.w[c];
+    }
+    a.wsum[t] = s;
+    a.obj[t] = 0.0;
+    a.done[t] = 0;
+    a.iters[t] = 0;
+}
+
+template <int C>
+__device__ __forceinline__ double gm_point(const GmArgs& a, const double (&w)[C], double wsum, int64_t i,
+                                           float (&x)[C]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < C; ++c) x[c] = a.x[c][i];
+    double s = (double)x[0] * w[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) s = s + (double)x[c] * w[c];
+    return s / wsum;
+}
+
+// squared distances of every collaborator to the current median, one block per
+// chunk; a finished tensor's chunks are skipped
+template <int C>
+__global__ __launch_bounds__(kNT) void k_gm_dist(GmArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double red[kNT / 64][kMaxC];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int ch = blockIdx.x; ch < a.nchunks; ch += gridDim.x) {
+        const ofl_gm_chunk k = a.chunks[ch];
+        if (a.done[k.tensor]) continue;
+        double w[C], acc[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            w[c] = a.W[k.tensor * kMaxC + c];
+            acc[c] = 0.0;
+        }
+        const double wsum = a.wsum[k.tensor];
+        for (int e = tid; e < k.len; e += kNT) {
+            float x[C];
+            const double m = gm_point<C>(a, w, wsum, k.start + e, x);
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const double r = m - (double)x[c];
+                acc[c] = acc[c] + r * r;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            double s = acc[c];
+            for (int off = 32; off; off >>= 1) s = s + __shfl_down(s, off);
+            if (lane == 0) red[wave][c] = s;
+        }
+        __syncthreads();
+        if (tid < C) a.partial[(int64_t)ch * kMaxC + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+        __syncthreads();
+    }
+}
+
+// NumPy's pairwise sum of n <= 16 values (weights.sum()): in order below 8,
+// eight accumulators combined as a tree from 8 on
+__device__ double np_sum16(const double* v, int n) {
+#pragma clang fp contract(off)
+    if (n < 8) {
+        double r = 0.0;
+        for (int k = 0; k < n; ++k) r = r + v[k];
+        return r;
+    }
+    double r[8];
+    for (int k = 0; k < 8; ++k) r[k] = v[k];
+    int k = 8;
+    for (; k < n - (n % 8); k += 8)
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + v[k + j];
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; k < n; ++k) res = res + v[k];
+    return res;
+}
+
+// After distance pass `pass` (0: the first average): add every tensor's chunk
+// partials in chunk order, d_c = sqrt, objective sum_c W_c d_c with the weights
+// the median was formed with, the reference's break test (strict <, so an
+// objective of 0 never breaks), and unless this was the last pass the next
+// weights W / max(eps, d), renormalised.  One 256-thread block per tensor.
+__global__ __launch_bounds__(kNT) void k_gm_update(GmArgs a, int pass, int last) {
+#pragma clang fp contract(off)
+    constexpr int kStage = 128;  // chunk rows staged at a time (16 KiB of LDS)
+    __shared__ double d[kMaxC], nw[kMaxC], stage[kStage * kMaxC];
+    const int t = blockIdx.x, lane = threadIdx.x;
+    if (a.done[t]) return;
+    // the partial rows go through LDS (coalesced loads by the whole block), then
+    // lane c runs collaborator c's add chain from LDS, loads issued eight ahead
+    // of the adds, as k_range_sums does
+    const int c0 = a.tchunk0[t], c1 = a.tchunk0[t + 1];
+    double s = 0.0;
+    for (int b = c0; b < c1; b += kStage) {
+        const int m = c1 - b < kStage ? c1 - b : kStage;
+        __syncthreads();
+        for (int k = lane; k < m * kMaxC; k += kNT) stage[k] = a.partial[(int64_t)b * kMaxC + k];
+        __syncthreads();
+        if (lane < a.nc) {
+            int k = 0;
+            for (; k + 8 <= m; k += 8) {
+                double v[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) v[q] = stage[(k + q) * kMaxC + lane];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) s = s + v[q];
+            }
+            for (; k < m; ++k) s = s + stage[k * kMaxC + lane];
+        }
+    }
+    if (lane < a.nc) d[lane] = sqrt(s);
+    __syncthreads();
+    if (lane) return;
+    double* W = a.W + t * kMaxC;
+    double obj = 0.0;
+    for (int c = 0; c < a.nc; ++c) obj = obj + W[c] * d[c];
+    const double prev = a.obj[t];
+    a.obj[t] = obj;
+    if (pass > 0) {
+        a.iters[t] = pass;
+        if (fabs(prev - obj) < a.ftol * obj) {
+            a.done[t] = 1;
+            return;
+        }
+    }
+    if (last) return;
+    for (int c = 0; c < a.nc; ++c) nw[c] = W[c] / (d[c] > a.eps ? d[c] : a.eps);
+    const double tot = np_sum16(nw, a.nc);
+    double ws = 0.0;
+    for (int c = 0; c < a.nc; ++c) {
+        const double w = nw[c] / tot;
+        W[c] = w;
+        ws = c ? ws + w : w;
+    }
+    a.wsum[t] = ws;
+}
+
+// the aggregate with every tensor's final weights, and the deltas as
+// k_wavg_delta writes them
+template <int C>
+__global__ __launch_bounds__(kNT) void k_gm_final(GmArgs a) {
+#pragma clang fp contract(off)
+    for (int ch = blockIdx.x; ch < a.nchunks; ch += gridDim.x) {
+        const ofl_gm_chunk k = a.chunks[ch];
+        double w[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) w[c] = a.W[k.tensor * kMaxC + c];
+        const double wsum = a.wsum[k.tensor];
+        for (int e = threadIdx.x; e < k.len; e += kNT) {
+            const int64_t i = k.start + e;
+            float x[C];
+            const double m = gm_point<C>(a, w, wsum, i, x);
+            const double dl = a.base ? m - (double)a.base[i] : m;
+            if (a.agg) a.agg[i] = m;
+            if (a.delta64) a.delta64[i] = dl;
+            if (a.delta32) a.delta32[i] = (float)dl;
+        }
+    }
+}
+
+// the delta of an aggregate arena on listed ranges, packed: float64 aggregate
+// -> agg - (double)base; float32 aggregate -> a float32 subtract
+template <typename T>
+__global__ __launch_bounds__(kNT) void k_agg_ranges(const T* agg, const float* base, const int64_t* start,
+                                                    const int64_t* dst, int nr, T* out) {
+#pragma clang fp contract(off)
+    const int64_t total = dst[nr];
+    for (int64_t j = (int64_t)blockIdx.x * kNT + threadIdx.x; j < total; j += (int64_t)gridDim.x * kNT) {
+        int lo = 0, hi = nr - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (dst[mid] <= j) lo = mid; else hi = mid - 1;
+        }
+        const int64_t i = start[lo] + (j - dst[lo]);
+        out[j] = base ? agg[i] - (T)base[i] : agg[i];
+    }
+}
+
+// k_range_sums for float32 values: the chain is a float32 add per element
+// (sum() over np.float32 scalars); the sum is stored widened
+__global__ __launch_bounds__(256) void k_range_sums32(const float* packed, const int64_t* dst, double* sums) {
+#pragma clang fp contract(off)
+    __shared__ float v[2048];
+    const int r = blockIdx.x;
+    const int64_t j0 = dst[r], j1 = dst[r + 1];
+    float s = 0.0f;
+    for (int64_t c0 = j0; c0 < j1; c0 += 2048) {
+        const int m = (int)(j1 - c0 < 2048 ? j1 - c0 : 2048);
+        __syncthreads();
+        for (int k = threadIdx.x; k < m; k += 256) v[k] = packed[c0 + k];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int k = 0;
+            for (; k + 8 <= m; k += 8) {
+                float t[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) t[q] = v[k + q];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) s = s + t[q];
+            }
+            for (; k < m; ++k) s = s + v[k];
+        }
+    }
+    if (threadIdx.x == 0) sums[r] = (double)s;
+}
+
+// k_seeds for a float32 sum: NumPy >= 2 scalar promotion keeps
+// np.float32(sum) * 13 + 7 in float32 (two roundings); hash() of a np.float32
+// is the hash of its value as a Python float
+__global__ __launch_bounds__(64) void k_seeds32(const double* sums, const int64_t* draws, int n, uint32_t* seeds) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    float t = (float)sums[i] * 13.0f;
+    t = t + 7.0f;
+    const int64_t h = py_hash_double((double)t) + draws[i];
+    seeds[i] = (uint32_t)(((h % 65536) + 65536) % 65536);
+}
+
+}  // namespace agg
+
+namespace {
+template <int C>
+void launch_median(const agg::MedArgs& a, int vec, hipStream_t st) {
+    hipLaunchKernelGGL(agg::k_median<C>, dim3(grid_for(a.n, 4)), dim3(agg::kNT), 0, st, a, vec);
+}
+template <int C>
+void launch_gm_dist(const agg::GmArgs& a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(agg::k_gm_dist<C>, dim3(grid), dim3(agg::kNT), 0, st, a);
+}
+template <int C>
+void launch_gm_final(const agg::GmArgs& a, int grid, hipStream_t st) {
+    hipLaunchKernelGGL(agg::k_gm_final<C>, dim3(grid), dim3(agg::kNT), 0, st, a);
+}
+#define OFL_FOR_C16(F, c, ...)                                                                      \
+    switch (c) {                                                                                    \
+        case 1: F<1>(__VA_ARGS__); break;   case 2: F<2>(__VA_ARGS__); break;                       \
+        case 3: F<3>(__VA_ARGS__); break;   case 4: F<4>(__VA_ARGS__); break;                       \
+        case 5: F<5>(__VA_ARGS__); break;   case 6: F<6>(__VA_ARGS__); break;                       \
+        case 7: F<7>(__VA_ARGS__); break;   case 8: F<8>(__VA_ARGS__); break;                       \
+        case 9: F<9>(__VA_ARGS__); break;   case 10: F<10>(__VA_ARGS__); break;                     \
+        case 11: F<11>(__VA_ARGS__); break; case 12: F<12>(__VA_ARGS__); break;                     \
+        case 13: F<13>(__VA_ARGS__); break; case 14: F<14>(__VA_ARGS__); break;                     \
+        case 15: F<15>(__VA_ARGS__); break; default: F<16>(__VA_ARGS__); break;                     \
+    }
+
+size_t gm_align(size_t v) { return (v + 255) & ~(size_t)255; }
+}  // namespace
+
+extern "C" {
+
+int ofl_median_delta(int ncollab, const float* const* xs, const float* base, int64_t n, float* median_out,
+                     float* delta_out, void* stream) {
+    if (ncollab < 1 || !xs) return afail(OFL_EINVAL, "median: need at least one collaborator");
+    if (ncollab > agg::kMedMaxC) return afail(OFL_EINVAL, "median: at most 128 collaborators");
+    if (n < 0) return afail(OFL_EINVAL, "median: negative size");
+    for (int c = 0; c < ncollab; ++c)
+        if (!xs[c]) return afail(OFL_EINVAL, "median: null collaborator tensor");
+    if (n == 0 || (!median_out && !delta_out)) return OFL_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (ncollab <= agg::kMaxC) {
+        agg::MedArgs a{};
+        uintptr_t al = reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(median_out) |
+                       reinterpret_cast<uintptr_t>(delta_out);
+        for (int c = 0; c < ncollab; ++c) {
+            a.x[c] = xs[c];
+            al |= reinterpret_cast<uintptr_t>(xs[c]);
+        }
+        a.base = base;
+        a.med = median_out;
+        a.delta = delta_out;
+        a.n = n;
+        OFL_FOR_C16(launch_median, ncollab, a, (al & 15u) ? 0 : 1, st)
+    } else {
+        agg::MedArgsN a{};
+        for (int c = 0; c < ncollab; ++c) a.x[c] = xs[c];
+        a.nc = ncollab;
+        a.base = base;
+        a.med = median_out;
+        a.delta = delta_out;
+        a.n = n;
+        const int64_t want = (n + agg::kMedLdsNT - 1) / agg::kMedLdsNT;
+        const int g = (int)std::min<int64_t>(want, (int64_t)grid_for(n, 1) * 4);
+        hipLaunchKernelGGL(agg::k_median_lds, dim3(g), dim3(agg::kMedLdsNT), 0, st, a);
+    }
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+size_t ofl_gmedian_workspace_bytes(int ntensors, int nchunks) {
+    const size_t T = (size_t)std::max(ntensors, 1), K = (size_t)std::max(nchunks, 1);
+    return gm_align(8 * T * agg::kMaxC) + 2 * gm_align(8 * T) + 2 * gm_align(4 * T) + gm_align(8 * K * agg::kMaxC) + 256;
+}
+
+int ofl_gmedian_delta(int ncollab, const float* const* xs, const double* w0, int maxiter, double eps, double ftol,
+                      const float* base, int ntensors, const ofl_gm_chunk* chunks_dev, int nchunks,
+                      const int32_t* tensor_chunk0_dev, double* agg_out, double* delta64_out, float* delta32_out,
+                      int32_t* iters_out, void* ws, size_t ws_bytes, void* stream) {
+    if (ncollab < 1 || !xs || !w0) return afail(OFL_EINVAL, "geometric median: need at least one collaborator");
+    if (ncollab > agg::kMaxC) return afail(OFL_EINVAL, "geometric median: at most 16 collaborators");
+    if (ntensors < 1 || nchunks < 0 || maxiter < 0) return afail(OFL_EINVAL, "geometric median: bad sizes");
+    if (!tensor_chunk0_dev || (nchunks && !chunks_dev)) return afail(OFL_EINVAL, "geometric median: null chunk table");
+    if (!ws || ws_bytes < ofl_gmedian_workspace_bytes(ntensors, nchunks))
+        return afail(OFL_ESPACE, "geometric median: workspace too small");
+    const size_t T = (size_t)ntensors, K = (size_t)std::max(nchunks, 1);
+    char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+    agg::GmArgs a{};
+    agg::GmW0 init{};
+    for (int c = 0; c < ncollab; ++c) {
+        if (!xs[c]) return afail(OFL_EINVAL, "geometric median: null collaborator tensor");
+        a.x[c] = xs[c];
+        init.w[c] = w0[c];
+    }
+    a.nc = ncollab;
+    a.chunks = chunks_dev;
+    a.nchunks = nchunks;
+    a.tchunk0 = tensor_chunk0_dev;
+    a.nt = ntensors;
+    a.W = reinterpret_cast<double*>(w);        w += gm_align(8 * T * agg::kMaxC);
+    a.wsum = reinterpret_cast<double*>(w);     w += gm_align(8 * T);
+    a.obj = reinterpret_cast<double*>(w);      w += gm_align(8 * T);
+    a.done = reinterpret_cast<int32_t*>(w);    w += gm_align(4 * T);
+    a.iters = reinterpret_cast<int32_t*>(w);   w += gm_align(4 * T);
+    a.partial = reinterpret_cast<double*>(w);  w += gm_align(8 * K * agg::kMaxC);
+    if (iters_out) a.iters = iters_out;
+    a.eps = eps;
+    a.ftol = ftol;
+    a.base = base;
+    a.agg = agg_out;
+    a.delta64 = delta64_out;
+    a.delta32 = delta32_out;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int grid = std::max(1, std::min(nchunks, cus * 8));
+    hipLaunchKernelGGL(agg::k_gm_init, dim3((ntensors + 63) / 64), dim3(64), 0, st, a, init);
+    for (int pass = 0; pass <= maxiter; ++pass) {
+        if (nchunks) OFL_FOR_C16(launch_gm_dist, ncollab, a, grid, st)
+        hipLaunchKernelGGL(agg::k_gm_update, dim3(ntensors), dim3(agg::kNT), 0, st, a, pass, pass == maxiter ? 1 : 0);
+    }
+    if (nchunks && (agg_out || delta64_out || delta32_out)) OFL_FOR_C16(launch_gm_final, ncollab, a, grid, st)
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_agg_delta_seeds(const void* agg_dev, int agg_is_f64, const float* base, int nranges, const int64_t* starts_dev,
+                        const int64_t* dst_dev, int64_t total, const int64_t* draws_dev, uint32_t* seeds_dev,
+                        double* sums_dev, void* packed_dev, void* stream) {
+    if (nranges < 1 || total < 0) return afail(OFL_EINVAL, "agg seeds: bad sizes");
+    if (!agg_dev || !starts_dev || !dst_dev || !draws_dev || !seeds_dev || !sums_dev || (total > 0 && !packed_dev))
+        return afail(OFL_EINVAL, "agg seeds: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int g = grid_for(std::max<int64_t>(total, 1), 1), gs = (nranges + 63) / 64;
+    if (agg_is_f64) {
+        double* packed = static_cast<double*>(packed_dev);
+        if (total > 0)
+            hipLaunchKernelGGL(agg::k_agg_ranges<double>, dim3(g), dim3(agg::kNT), 0, st,
+                               static_cast<const double*>(agg_dev), base, starts_dev, dst_dev, nranges, packed);
+        hipLaunchKernelGGL(agg::k_range_sums, dim3(nranges), dim3(256), 0, st, packed, dst_dev, sums_dev);
+        hipLaunchKernelGGL(agg::k_seeds, dim3(gs), dim3(64), 0, st, sums_dev, draws_dev, nranges, seeds_dev);
+    } else {
+        float* packed = static_cast<float*>(packed_dev);
+        if (total > 0)
+            hipLaunchKernelGGL(agg::k_agg_ranges<float>, dim3(g), dim3(agg::kNT), 0, st,
+                               static_cast<const float*>(agg_dev), base, starts_dev, dst_dev, nranges, packed);
+        hipLaunchKernelGGL(agg::k_range_sums32, dim3(nranges), dim3(256), 0, st, packed, dst_dev, sums_dev);
+        hipLaunchKernelGGL(agg::k_seeds32, dim3(gs), dim3(64), 0, st, sums_dev, draws_dev, nranges, seeds_dev);
+    }
     AHIP(hipGetLastError());
     return OFL_OK;
 }

@@ -32,6 +32,61 @@ sys.path.insert(0, ROOT)
 PEAK_HBM_GBPS = 8000.0
 
 
+def robust(args, pipe, shapes, dev, collabs, w, base, out, nbytes, timed):
+    """--aggregation median | geometric_median: one JSON line with the round
+    end's step time, the aggregation kernels alone (median: bytes moved, 4 C + 4
+    + 4 per element with a base; geometric median: all passes of one call and
+    the rounds the tensors ran) and the unfused weighted-average round end on
+    the same arenas, interleaved."""
+    import torch
+    from openfl_amd import aggregation as A
+    C = len(collabs)
+    re = A.RoundEnd(pipe, shapes, dev, aggregation=args.aggregation)
+    re_u = A.RoundEnd(pipe, shapes, dev, fused=False)
+    t_r, t_u = [], []
+    for _ in range(3):
+        t_r.append(timed(lambda: re.run(collabs, w, base, payloads=False, out=out), args.steps, args.warmup))
+        t_u.append(timed(lambda: re_u.run(collabs, w, base, payloads=False, out=out), args.steps, args.warmup))
+    t_pay = timed(lambda: re.run(collabs, w, base, payloads=True, out=out), max(1, args.steps // 2), 1)
+    delta = torch.empty(re.arena_numel, dtype=torch.float32, device=dev)
+    n = re.arena_numel
+    if args.aggregation == "median":
+        t_k = timed(lambda: A._median_launch(collabs, base, n, delta=delta, device=dev), args.steps, args.warmup)
+        moved = n * (4 * C + 4 + 4)
+        kernel = {"kernel": "k_median (median + float32 delta)", "ms": round(1e3 * t_k, 4), "bytes_moved": moved,
+                  "GBps": round(moved / t_k / 1e9, 1), "frac_of_peak_hbm": round(moved / t_k / 1e9 / PEAK_HBM_GBPS, 4)}
+        w64 = A._f64_weights(w, C)
+        wsum = A.weight_sum(w64, 1)
+        t_w = timed(lambda: A._wavg_launch(collabs, w64, wsum, base, n, delta32=delta, device=dev),
+                    args.steps, args.warmup)
+        kernel["k_wavg_delta_same_bytes"] = {"ms": round(1e3 * t_w, 4), "GBps": round(moved / t_w / 1e9, 1)}
+    else:
+        agg = torch.empty(n, dtype=torch.float64, device=dev)
+        w0 = A._gm_start_weights(w, C)
+        t_k = timed(lambda: re._gm.launch(collabs, w0, 4, 1e-5, 1e-6, base, agg=agg, delta32=delta, device=dev),
+                    args.steps, args.warmup)
+        it = re._gm.iters[:len(shapes)].cpu().numpy()
+        t_0 = timed(lambda: re._gm.launch(collabs, w0, 0, 1e-5, 1e-6, base, agg=agg, delta32=delta, device=dev),
+                    args.steps, args.warmup)
+        kernel = {"kernel": "ofl_gmedian_delta (maxiter 4: up to 5 distance passes + the final average)",
+                  "ms": round(1e3 * t_k, 4), "ms_maxiter0_one_distance_pass_plus_final": round(1e3 * t_0, 4),
+                  "ms_per_extra_round": round(1e3 * (t_k - t_0) / 4, 4),
+                  "rounds_min_max": [int(it.min()), int(it.max())],
+                  "tensors_by_rounds": {str(k): int((it == k).sum()) for k in sorted(set(it.tolist()))}}
+    line = {"metric": f"GiB/s aggregator round end ({args.aggregation} + delta + Eden encode/decode + apply), "
+                      "device-resident",
+            "value": round(nbytes / min(t_r) / 2 ** 30, 3), "unit": "GiB/s", "n_gpus": 1, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * min(t_r), 3), "higher_is_better": True,
+            "dtype": "f32" if args.aggregation == "median" else "f32/f64",
+            "data": "synthetic N(0, 0.01^2) updates and base, resident in HBM",
+            "config": {"workload": args.workload, "tensors": len(shapes), "bytes": nbytes, "collaborators": C,
+                       "n_bits": 8, "seed_mode": args.seed_mode, "aggregation": args.aggregation},
+            "also": {"with_payload_d2h": {"ms_per_step": round(1e3 * t_pay, 3)},
+                     "unfused_weighted_average_same_interleave": {"ms_per_step": round(1e3 * min(t_u), 3)},
+                     "aggregation_alone": kernel}}
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="resnet50_fp32")
@@ -40,6 +95,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed-mode", default="fast")
     ap.add_argument("--host-steps", type=int, default=1, help="steps of the per-tensor host call pattern (0: skip)")
+    ap.add_argument("--aggregation", default="weighted_average", choices=["weighted_average", "median", "geometric_median"],
+                    help="median / geometric_median: the round end with that aggregator (never fused), its "
+                         "aggregation kernels alone, and the unfused weighted-average round end beside it")
     args = ap.parse_args()
 
     import torch
@@ -71,6 +129,9 @@ def main():
             fn()
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / steps
+
+    if args.aggregation != "weighted_average":
+        return robust(args, pipe, shapes, dev, collabs, w, base, out, nbytes, timed)
 
     t_dev = timed(lambda: re.run(collabs, w, base, payloads=False, out=out), args.steps, args.warmup)
     t_pay = timed(lambda: re.run(collabs, w, base, payloads=True, out=out), max(1, args.steps // 2), 1)
