@@ -89,7 +89,7 @@ void ofl_eden_plan_destroy(ofl_eden_plan_t plan);
  * gaps and tails; there are then at least two waves (the large slices split
  * in halves).  wave_bytes < 0 or streams == 0 keep the current value.  Only
  * before the plan's first encode/decode; the workspace size changes with it.
- * Default: 2 GiB waves, 2 streams (env OFL_EDEN_WAVE_MIB / OFL_EDEN_STREAMS
+ * Default: 128 MiB waves, 2 streams (env OFL_EDEN_WAVE_MIB / OFL_EDEN_STREAMS
  * override the default; DESIGN.md section 3.6 has the measurements). */
 int ofl_eden_plan_set_schedule(ofl_eden_plan_t plan, int64_t wave_bytes, int streams);
 int ofl_eden_plan_get_schedule(ofl_eden_plan_t plan, int64_t* wave_bytes, int* streams);
@@ -97,18 +97,17 @@ int ofl_eden_plan_num_waves(ofl_eden_plan_t plan);
 /* Kernel choice for the large slices' row passes (no reference counterpart;
  * outputs bit-identical either way): -1 auto (launches of fewer than 5 tiles
  * per CU use the two-blocks-per-CU kernels, the rest the persistent
- * prefetching ones; env OFL_EDEN_ROW2 / OFL_EDEN_ROW2_TPC override the auto
- * rule), 0 always persistent, 1 always two blocks per CU.  The schedule
- * depends on it (a 5-pass slice above the wave size splits into sub-waves
- * only with the two-blocks-per-CU kernels), so it is rebuilt: only before
- * the plan's first encode/decode (OFL_EINVAL afterwards). */
+ * prefetching ones), 0 always persistent, 1 always two blocks per CU.  The
+ * schedule depends on it (a 5-pass slice above the wave size splits into
+ * sub-waves only with the two-blocks-per-CU kernels), so it is rebuilt: only
+ * before the plan's first encode/decode (OFL_EINVAL afterwards). */
 int ofl_eden_plan_set_row2(ofl_eden_plan_t plan, int mode);
 /* Tile pairs in the two-blocks-per-CU row passes that apply the D1 signs
  * (encode pass A, decode pass C; no reference counterpart, outputs
  * bit-identical either way): a block runs a tile and the one 2^(p-3)
  * elements up, whose sign words are the same, and hashes them once.
- * -1 auto (launches of more tiles than two per CU; env OFL_EDEN_PAIR
- * overrides), 0 never, 1 whenever the launch holds slices of >= 2^18.
+ * -1 auto (launches of more tiles than two per CU), 0 never, 1 whenever the
+ * launch holds slices of >= 2^18.
  * The sub-waves of a split 5-pass slice get their paired tile tables when
  * the schedule is built, so it is rebuilt: only before the plan's first
  * encode/decode (OFL_EINVAL afterwards). */
@@ -116,14 +115,13 @@ int ofl_eden_plan_set_pair(ofl_eden_plan_t plan, int mode);
 /* Launches of the tiny (<= 2^10) and small (2^11..2^15) slices (no reference
  * counterpart; outputs bit-identical either way): 1 one small-set launch of
  * 1024-thread workgroups for all of them, 0 one launch per size class, -1 the
- * default (1; env OFL_EDEN_SSET=0 selects 0).  Before the first encode/decode. */
+ * default (1).  Before the first encode/decode. */
 int ofl_eden_plan_set_sset(ofl_eden_plan_t plan, int mode);
 /* A plan whose large slices fit one wave and whose single-level middle passes
  * share one k_col_multi launch runs its small-set groups inside that launch,
  * on the caller's stream (no side stream, no fork / join): 1 yes, 0 the
- * small-set launch on the side stream, -1 the default (1; env
- * OFL_EDEN_FUSESET=0 selects 0).  Outputs bit-identical either way.  Before
- * the first encode/decode. */
+ * small-set launch on the side stream, -1 the default (1).  Outputs
+ * bit-identical either way.  Before the first encode/decode. */
 int ofl_eden_plan_set_fuse(ofl_eden_plan_t plan, int mode);
 
 /* Totals: slices (= length of the scales array), planes-arena bytes,

@@ -58,22 +58,31 @@
 
 #define DEVI __device__ __forceinline__
 
-#ifndef OFL_COL_SC1
-#define OFL_COL_SC1 1
-#endif
-// cache policy of the large slices' arena I/O (kIoLdAux / kIoStAux below):
-// nt both ways -- at MALL-sized waves the streamed x / y / plane bytes then
-// do not push a wave's intermediates out of the Infinity Cache (Llama-3-8B
-// 444-447 -> 471-472 GiB/s, the 1 GiB set 473-475 -> 508-509,
-// profiles/r06_io_nt_ab.txt)
-#ifndef OFL_IO_LD_AUX
-#define OFL_IO_LD_AUX 2
-#endif
-#ifndef OFL_IO_ST_AUX
-#define OFL_IO_ST_AUX 2
-#endif
-
 namespace ofl {
+
+// Cache policy of the large-slice passes' buffer accesses (aux operand on
+// gfx950: bit 0 = sc0, bit 1 = nt, bit 4 = sc1), each at its measured winner.
+// The intermediate (ws) accesses.  Stores sc1: the line leaves the XCD's L2
+// as it is written instead of at the kernel boundary, where a pass would
+// otherwise leave up to 32 MiB of dirty L2 behind for the next launch to wait
+// on (Llama-3-8B 483.7-483.9 -> 486.5-488.1 GiB/s, the 1 GiB set 514.6-517.5
+// -> 525.2-525.6, profiles/r06_sc1_ab.txt)
+constexpr int kLdAux = 0;
+constexpr int kStAux = 16;
+// The large slices' once-read / once-written arena I/O (x loads, y stores
+// and the yadd loads, bit-plane loads and stores), separately from the
+// intermediates', which MALL-sized waves re-read from the cache: nt both ways
+// -- at MALL-sized waves the streamed x / y / plane bytes then do not push a
+// wave's intermediates out of the Infinity Cache (Llama-3-8B 444-447 ->
+// 471-472 GiB/s, the 1 GiB set 473-475 -> 508-509, profiles/r06_io_nt_ab.txt)
+constexpr int kIoLdAux = 2;
+constexpr int kIoStAux = 2;
+// k_dec_rowC2's intermediate loads: the decode's last read of a wave's ws
+constexpr int kDecC2LdAux = 0;
+// k_enc_rowC2's: the default policy since the arena I/O went nt (round 6:
+// 478.5-479.2 vs 476.7-478.7 GiB/s with nt, profiles/r06_rowc2ld_ab.txt; nt
+// had won at the 2 GiB waves of round 3, profiles/r03_nt_ab.txt)
+constexpr int kRowC2LdAux = 0;
 
 // ---------------------------------------------------------------------------
 // Descriptors (host-built once per plan, uploaded on first use)
@@ -471,24 +480,6 @@ DEVI void unpack_centroids32(const uint32_t (&w)[8], const float* cen, float (&v
 #pragma unroll
     for (int g = 0; g < 4; ++g) unpack_group(xl[g], xh[g], cen, &v[8 * g]);
 }
-// 64 contiguous values -> 8 plane words of 64 bits (bit t = element t)
-DEVI float quant_pack64(const float (&v)[64], float ysc, float zm64, const QTab* q, uint64_t (&w)[8]) {
-    float dot = 0.f;
-    const float m64 = ysc * zm64;
-    uint32_t xl[8], xh[8];
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        float vg[8];
-        pin_group<8>(&v[8 * g], vg);
-        quant_group(vg, m64, q, xl[g], xh[g], dot);
-        asm volatile("" : "+v"(xl[g]), "+v"(xh[g]), "+v"(dot) :: "memory");  // group done before the next
-    }
-    uint32_t wl[8], wh[8];
-    tr_bytes8(xl, xh, wl, wh);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = (uint64_t)wl[i] | ((uint64_t)wh[i] << 32);
-    return dot * ysc;
-}
 DEVI void unpack_centroids64(const uint64_t (&w)[8], const float* cen, float (&v)[64]) {
     uint32_t il[8], ih[8], xl[8], xh[8];
 #pragma unroll
@@ -496,18 +487,6 @@ DEVI void unpack_centroids64(const uint64_t (&w)[8], const float* cen, float (&v
     tr_bytes8(il, ih, xl, xh);
 #pragma unroll
     for (int g = 0; g < 8; ++g) unpack_group(xl[g], xh[g], cen, &v[8 * g]);
-}
-DEVI void store_plane_word64(uint8_t* p, uint64_t w) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    if ((a & 7u) == 0) {
-        *reinterpret_cast<uint64_t*>(p) = w;
-    } else if ((a & 3u) == 0) {
-        reinterpret_cast<uint32_t*>(p)[0] = (uint32_t)w;
-        reinterpret_cast<uint32_t*>(p)[1] = (uint32_t)(w >> 32);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) p[q] = (uint8_t)(w >> (8 * q));
-    }
 }
 DEVI uint64_t load_plane_word64(const uint8_t* p) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(p);
@@ -520,10 +499,6 @@ DEVI uint64_t load_plane_word64(const uint8_t* p) {
     for (int q = 0; q < 8; ++q) r |= (uint64_t)p[q] << (8 * q);
     return r;
 }
-DEVI void store_planes64(uint8_t* plane0, uint32_t e, int64_t stride, int nbits, const uint64_t (&w)[8]) {
-    uint8_t* p = plane0 + (e >> 3);
-    for (int i = 0; i < nbits; ++i) store_plane_word64(p + (int64_t)i * stride, w[i]);
-}
 DEVI void load_planes64(const uint8_t* plane0, uint32_t e, int64_t stride, int nbits, uint64_t (&w)[8]) {
     const uint8_t* p = plane0 + (e >> 3);
 #pragma unroll
@@ -533,7 +508,7 @@ DEVI void load_planes64(const uint8_t* plane0, uint32_t e, int64_t stride, int n
 
 DEVI void store_plane_word(uint8_t* p, uint32_t w) {
     if ((reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
-        if constexpr ((OFL_IO_ST_AUX & 2) != 0) __builtin_nontemporal_store(w, reinterpret_cast<uint32_t*>(p));
+        if constexpr ((kIoStAux & 2) != 0) __builtin_nontemporal_store(w, reinterpret_cast<uint32_t*>(p));
         else *reinterpret_cast<uint32_t*>(p) = w;
     } else {
         p[0] = (uint8_t)w; p[1] = (uint8_t)(w >> 8); p[2] = (uint8_t)(w >> 16); p[3] = (uint8_t)(w >> 24);
@@ -1073,7 +1048,6 @@ constexpr size_t kRowTab = kRowSmem;
 constexpr size_t kRowRed = kRowTab + sizeof(TileTab);
 constexpr size_t kRowExtra = kRowRed + 64;
 constexpr size_t kRowSmemA = kRowExtra;
-constexpr size_t kRowSmemQ = kRowExtra + sizeof(QTab);
 constexpr size_t kRowSmemC = kRowExtra + sizeof(float) * 256;
 
 // block-uniform descriptor/scalar reads: loads issued after the loop's global
@@ -1166,52 +1140,6 @@ __device__ uint8_t raw_load_u8(rsrc_t r, int voff, int soff, int aux) __asm("llv
 __device__ void raw_store_f32x4(f32x4 v, rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.store.v4f32");
 __device__ void raw_store_f32(float v, rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.store.f32");
 
-// Cache policy of the large-slice passes' intermediate (ws) buffer accesses
-// (aux operand on gfx950: bit 0 = sc0, bit 1 = nt, bit 4 = sc1).  Tuning
-// constants for A/B builds (tools/build_flags_variant.sh ... -DOFL_LD_AUX=2),
-// not a platform switch.  Stores sc1: the line leaves the XCD's L2 as it is
-// written instead of at the kernel boundary, where a pass would otherwise
-// leave up to 32 MiB of dirty L2 behind for the next launch to wait on
-// (Llama-3-8B 483.7-483.9 -> 486.5-488.1 GiB/s, the 1 GiB set 514.6-517.5 ->
-// 525.2-525.6, profiles/r06_sc1_ab.txt)
-#ifndef OFL_LD_AUX
-#define OFL_LD_AUX 0
-#endif
-#ifndef OFL_ST_AUX
-#define OFL_ST_AUX 16
-#endif
-constexpr int kLdAux = OFL_LD_AUX;
-constexpr int kStAux = OFL_ST_AUX;
-// ... of the large slices' once-read / once-written arena I/O (x loads, y
-// stores and the yadd loads, bit-plane loads and stores), separately from
-// the intermediates', which MALL-sized waves re-read from the cache
-constexpr int kIoLdAux = OFL_IO_LD_AUX;
-// k_dec_rowC2's intermediate loads: the decode's last read of a wave's ws
-#ifndef OFL_DECC2_LD_AUX
-#define OFL_DECC2_LD_AUX 0
-#endif
-constexpr int kDecC2LdAux = OFL_DECC2_LD_AUX;
-constexpr int kIoStAux = OFL_IO_ST_AUX;
-
-// Ladder builds (diagnostics only, WRONG results; tools/r06_ladder.sh):
-// -DOFL_LADDER=1 the large-slice passes keep only their tile loads and
-// stores (same addresses, layouts and bytes), =2 adds the butterflies and
-// the LDS exchanges, =3 adds the sign generation (D1 hashes, the D2 byte
-// table); 0 (the product) adds the quantiser / plane pack, the centroid
-// unpack and the block reductions.  The partial sums are then written as 1.
-#ifndef OFL_LADDER
-#define OFL_LADDER 0
-#endif
-constexpr int kLadder = OFL_LADDER;
-// (=5: the product without the sign generation, the bound of cheaper signs)
-constexpr bool kLadFly = kLadder == 0 || kLadder >= 2;   // butterflies + exchanges
-constexpr bool kLadSign = kLadder == 0 || kLadder == 3;  // sign generation
-constexpr bool kLadFull = kLadder == 0 || kLadder == 5;  // quantiser, unpack, reductions
-// the memory-only rungs' stand-ins: a plane word from 4 values, values from a plane byte
-DEVI uint32_t lad_word(float a, float b, float c, float d) {
-    return __float_as_uint(a) ^ __float_as_uint(b) ^ __float_as_uint(c) ^ __float_as_uint(d);
-}
-
 // word 3 = 0x00020000: 32-bit data format, as the gfx9 family expects
 DEVI rsrc_t mk_rsrc(const void* p, uint32_t bytes) {
     const uint64_t a = reinterpret_cast<uint64_t>(p);
@@ -1223,97 +1151,21 @@ DEVI rsrc_t mk_rsrc(const void* p, uint32_t bytes) {
     return r;
 }
 
-// Storage format of the large-slice intermediates.  32 (the product): fp32.
-// A/B stubs of narrower intermediates (WRONG results,
-// memory pattern only, tools/r06_ws_ab.sh): 16 = the high 16 bits of each
-// fp32 (2 B per element), 24 = split planes, the high 16 bits at byte 2e of
-// the slice's ws and the next 8 bits at byte 2P + e (3 B per element).
-#ifndef OFL_WS_FMT
-#define OFL_WS_FMT 32
-#endif
-constexpr int kWsFmt = OFL_WS_FMT;
-static_assert(kWsFmt == 32 || kWsFmt == 24 || kWsFmt == 16, "OFL_WS_FMT: 32, 24 or 16");
-__device__ uint16_t raw_load_u16(rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.load.i16");
-__device__ uint8_t raw_load_u8w(rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.load.i8");
-__device__ int raw_load_i32w(rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.load.i32");
-__device__ i32x2 raw_load_i32x2w(rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.load.v2i32");
-__device__ void raw_store_u16(uint16_t v, rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.store.i16");
-__device__ void raw_store_u8(uint8_t v, rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.store.i8");
-__device__ void raw_store_i32(int v, rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.store.i32");
-__device__ void raw_store_i32x2(i32x2 v, rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.store.v2i32");
-// a view of the intermediate elements [i0, i0 + bytes / 4) of a slice whose
-// ws starts at sw (2^logp elements); offsets below are fp32 byte offsets
-struct WsR { rsrc_t h, l; };
-DEVI WsR ws_rsrc(const float* sw, int logp, size_t i0, uint32_t bytes) {
-    WsR w;
-    if constexpr (kWsFmt == 32) {
-        w.h = mk_rsrc(sw + i0, bytes);
-        w.l = w.h;
-    } else {
-        const uint8_t* b = reinterpret_cast<const uint8_t*>(sw);
-        w.h = mk_rsrc(b + 2 * i0, bytes / 2);
-        w.l = mk_rsrc(b + (2ull << logp) + i0, kWsFmt == 24 ? bytes / 4 : 0u);
-    }
-    return w;
-}
-DEVI float ws_ld1(const WsR& w, uint32_t vo, uint32_t so, int aux) {
-    if constexpr (kWsFmt == 32) return raw_load_f32(w.h, (int)vo, (int)so, aux);
-    uint32_t u = (uint32_t)raw_load_u16(w.h, (int)(vo >> 1), (int)(so >> 1), aux) << 16;
-    if constexpr (kWsFmt == 24) u |= (uint32_t)raw_load_u8w(w.l, (int)(vo >> 2), (int)(so >> 2), aux) << 8;
-    return __uint_as_float(u);
-}
-DEVI void ws_st1(const WsR& w, uint32_t vo, uint32_t so, float v, int aux) {
-    if constexpr (kWsFmt == 32) { raw_store_f32(v, w.h, (int)vo, (int)so, aux); return; }
-    const uint32_t u = __float_as_uint(v);
-    raw_store_u16((uint16_t)(u >> 16), w.h, (int)(vo >> 1), (int)(so >> 1), aux);
-    if constexpr (kWsFmt == 24) raw_store_u8((uint8_t)(u >> 8), w.l, (int)(vo >> 2), (int)(so >> 2), aux);
-}
-DEVI f32x4 ws_ld4(const WsR& w, uint32_t vo, uint32_t so, int aux) {
-    if constexpr (kWsFmt == 32) return raw_load_f32x4(w.h, (int)vo, (int)so, aux);
-    const i32x2 h = raw_load_i32x2w(w.h, (int)(vo >> 1), (int)(so >> 1), aux);
-    uint32_t l = 0;
-    if constexpr (kWsFmt == 24) l = (uint32_t)raw_load_i32w(w.l, (int)(vo >> 2), (int)(so >> 2), aux);
-    const uint32_t h0 = (uint32_t)h.x, h1 = (uint32_t)h.y;
-    f32x4 q;
-    q.x = __uint_as_float((h0 << 16) | ((l & 0xffu) << 8));
-    q.y = __uint_as_float((h0 & 0xffff0000u) | (((l >> 8) & 0xffu) << 8));
-    q.z = __uint_as_float((h1 << 16) | (((l >> 16) & 0xffu) << 8));
-    q.w = __uint_as_float((h1 & 0xffff0000u) | ((l >> 24) << 8));
-    return q;
-}
-DEVI void ws_st4(const WsR& w, uint32_t vo, uint32_t so, f32x4 q, int aux) {
-    if constexpr (kWsFmt == 32) { raw_store_f32x4(q, w.h, (int)vo, (int)so, aux); return; }
-    const uint32_t a0 = __float_as_uint(q.x), a1 = __float_as_uint(q.y), a2 = __float_as_uint(q.z),
-                   a3 = __float_as_uint(q.w);
-    const i32x2 h = {(int)((a0 >> 16) | (a1 & 0xffff0000u)), (int)((a2 >> 16) | (a3 & 0xffff0000u))};
-    raw_store_i32x2(h, w.h, (int)(vo >> 1), (int)(so >> 1), aux);
-    if constexpr (kWsFmt == 24)
-        raw_store_i32((int)(((a0 >> 8) & 0xffu) | (a1 & 0xff00u) | ((a2 & 0xff00u) << 8) | ((a3 & 0xff00u) << 16)),
-                      w.l, (int)(vo >> 2), (int)(so >> 2), aux);
-}
-// element i of a slice's intermediate through a plain pointer (k_col)
-DEVI float ws_pld(const float* sw, int logp, uint32_t i) {
-    if constexpr (kWsFmt == 32) return sw[i];
-    const uint8_t* b = reinterpret_cast<const uint8_t*>(sw);
-    uint32_t u = (uint32_t)reinterpret_cast<const uint16_t*>(b)[i] << 16;
-    if constexpr (kWsFmt == 24) u |= (uint32_t)b[(2ull << logp) + i] << 8;
-    return __uint_as_float(u);
-}
+// The large-slice intermediates (ws) are fp32; offsets below are byte offsets
+// into a buffer view (mk_rsrc) of a tile or a slice
+DEVI float ws_ld1(rsrc_t r, uint32_t vo, uint32_t so, int aux) { return raw_load_f32(r, (int)vo, (int)so, aux); }
+DEVI void ws_st1(rsrc_t r, uint32_t vo, uint32_t so, float v, int aux) { raw_store_f32(v, r, (int)vo, (int)so, aux); }
+DEVI f32x4 ws_ld4(rsrc_t r, uint32_t vo, uint32_t so, int aux) { return raw_load_f32x4(r, (int)vo, (int)so, aux); }
+DEVI void ws_st4(rsrc_t r, uint32_t vo, uint32_t so, f32x4 q, int aux) { raw_store_f32x4(q, r, (int)vo, (int)so, aux); }
+// element i of a slice's intermediate through a plain pointer (k_col).
 // SC1: a relaxed agent-scope store, i.e. global_store ... sc1 (as the
-// buffer stores' OFL_ST_AUX): the middle passes of col_body (ResNet-50's
+// buffer stores' kStAux): the middle passes of col_body (ResNet-50's
 // small slices: 0.245 -> 0.239 ms; on the 2^29 slices' outer level-1 passes
 // it lost 0.3 %, so those keep plain stores; profiles/r06_colsc1_ab.txt)
 template <bool SC1 = false>
-DEVI void ws_pst(float* sw, int logp, uint32_t i, float v) {
-    if constexpr (kWsFmt == 32 && SC1 && OFL_COL_SC1) {
-        __hip_atomic_store(&sw[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    if constexpr (kWsFmt == 32) { sw[i] = v; return; }
-    uint8_t* b = reinterpret_cast<uint8_t*>(sw);
-    const uint32_t u = __float_as_uint(v);
-    reinterpret_cast<uint16_t*>(b)[i] = (uint16_t)(u >> 16);
-    if constexpr (kWsFmt == 24) b[(2ull << logp) + i] = (uint8_t)(u >> 8);
+DEVI void ws_pst(float* sw, uint32_t i, float v) {
+    if constexpr (SC1) __hip_atomic_store(&sw[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else sw[i] = v;
 }
 DEVI uint32_t tile_valid(int64_t len) {
     return len <= 0 ? 0u : (len >= (1 << kRowLog) ? (1u << kRowLog) : (uint32_t)len);
@@ -1401,45 +1253,41 @@ DEVI size_t ws_row_i0(const SliceDesc& D, uint32_t tile) {
 }
 DEVI float* ws_row_base(const KArgs& a, const SliceDesc& D, uint32_t tile) { return a.ws + D.ws_off + ws_row_i0(D, tile); }
 // the tile's ws view (bytes: fp32 extent of the tile's records)
-DEVI WsR ws_row(const KArgs& a, const SliceDesc& D, uint32_t tile, uint32_t bytes) {
-    return ws_rsrc(a.ws + D.ws_off, D.logp, ws_row_i0(D, tile), bytes);
+DEVI rsrc_t ws_row(const KArgs& a, const SliceDesc& D, uint32_t tile, uint32_t bytes) {
+    return mk_rsrc(ws_row_base(a, D, tile), bytes);
 }
 template <int AUX = kLdAux>
 DEVI void fetch_ws(const KArgs& a, const SliceDesc& D, uint32_t tile, bool live, uint32_t base3, float (&v)[64]) {
     if (D.perm) {
-        const WsR r = ws_row(a, D, tile, live ? (4u << (kRowLog + 1)) - 128u : 0u);
+        const rsrc_t r = ws_row(a, D, tile, live ? (4u << (kRowLog + 1)) - 128u : 0u);
         const uint32_t b = ws_row_idx(base3);
 #pragma unroll
         for (int k = 0; k < 64; ++k) v[k] = ws_ld1(r, b * 4u, (LT<RS::L3>::off(k) << 1) * 4u, AUX);
     } else {
-        const WsR r = ws_row(a, D, tile, live ? (4u << kRowLog) : 0u);
+        const rsrc_t r = ws_row(a, D, tile, live ? (4u << kRowLog) : 0u);
 #pragma unroll
         for (int k = 0; k < 64; ++k) v[k] = ws_ld1(r, base3 * 4u, LT<RS::L3>::off(k) * 4u, AUX);
     }
 }
 DEVI void store_ws(const KArgs& a, const SliceDesc& D, uint32_t tile, uint32_t base3, const float (&v)[64]) {
     if (D.perm) {
-        const WsR r = ws_row(a, D, tile, (4u << (kRowLog + 1)) - 128u);
+        const rsrc_t r = ws_row(a, D, tile, (4u << (kRowLog + 1)) - 128u);
         const uint32_t b = ws_row_idx(base3);
 #pragma unroll
         for (int k = 0; k < 64; ++k) ws_st1(r, b * 4u, (LT<RS::L3>::off(k) << 1) * 4u, v[k], kStAux);
     } else {
-        const WsR r = ws_row(a, D, tile, 4u << kRowLog);
+        const rsrc_t r = ws_row(a, D, tile, 4u << kRowLog);
 #pragma unroll
         for (int k = 0; k < 64; ++k) ws_st1(r, base3 * 4u, LT<RS::L3>::off(k) * 4u, v[k], kStAux);
     }
 }
 // ws tile in layout L (element bits 0, 1 in registers 0, 1) as float4s
-#ifndef OFL_ROW_WS4
-#define OFL_ROW_WS4 1  // A/B builds: 0 = the dword L3 tile I/O in k_enc_rowA / k_dec_rowC
-#endif
-constexpr bool kRowWs4 = OFL_ROW_WS4 != 0;
 template <Lay L>
 DEVI void fetch_ws4(const KArgs& a, const SliceDesc& D, uint32_t tile, bool live, uint32_t base, float (&v)[64],
                     int aux = kLdAux) {
     static_assert(LT<L>::rb(0) == 0 && LT<L>::rb(1) == 1, "float4 loads need element bits 0, 1 in registers 0, 1");
     const bool perm = D.perm;
-    const WsR r = ws_row(a, D, tile, live ? (perm ? (4u << (kRowLog + 1)) - 128u : 4u << kRowLog) : 0u);
+    const rsrc_t r = ws_row(a, D, tile, live ? (perm ? (4u << (kRowLog + 1)) - 128u : 4u << kRowLog) : 0u);
     const uint32_t b = perm ? ws_row_idx(base) : base;
 #pragma unroll
     for (int k = 0; k < 64; k += 4) {
@@ -1452,7 +1300,7 @@ template <Lay L>
 DEVI void store_ws4(const KArgs& a, const SliceDesc& D, uint32_t tile, uint32_t base, const float (&v)[64]) {
     static_assert(LT<L>::rb(0) == 0 && LT<L>::rb(1) == 1, "float4 stores need element bits 0, 1 in registers 0, 1");
     const bool perm = D.perm;
-    const WsR r = ws_row(a, D, tile, perm ? (4u << (kRowLog + 1)) - 128u : 4u << kRowLog);
+    const rsrc_t r = ws_row(a, D, tile, perm ? (4u << (kRowLog + 1)) - 128u : 4u << kRowLog);
     const uint32_t b = perm ? ws_row_idx(base) : base;
 #pragma unroll
     for (int k = 0; k < 64; k += 4) {
@@ -1460,13 +1308,6 @@ DEVI void store_ws4(const KArgs& a, const SliceDesc& D, uint32_t tile, uint32_t 
         const f32x4 q = {v[k], v[k + 1], v[k + 2], v[k + 3]};
         ws_st4(r, b * 4u, (perm ? ws_row_idx(o) : o) * 4u, q, kStAux);
     }
-}
-
-// the memory-only ladder rungs' stand-in for unpack_centroids64: a value per
-// byte of the plane words (no bit transposes, no centroid table)
-DEVI void lad_unpack64(const uint64_t (&w)[8], float (&v)[64]) {
-#pragma unroll
-    for (int r = 0; r < 64; ++r) v[r] = (float)((uint32_t)(w[r >> 3] >> (8 * (r & 7))) & 255u);
 }
 
 // the tile's 8-byte word of every plane (planes >= nbits read as 0).  A8: the
@@ -1499,7 +1340,7 @@ __global__ __launch_bounds__(kRowNT) void k_enc_rowA(KArgs a) {
     const TileWalk tw(a, reinterpret_cast<TileTab*>(smem + kRowTab), tid);
     int t = (int)blockIdx.x;
     if (t >= tw.total) return;
-    const uint32_t base1 = LT<RS::L1>::base(tid), base3 = LT<kRowWs4 ? RS::L3F : RS::L3>::base(tid);
+    const uint32_t base1 = LT<RS::L1>::base(tid), base3 = LT<RS::L3F>::base(tid);
     int si; uint32_t tile;
     tw.at(t, si, tile);
     float nx[64];
@@ -1516,91 +1357,16 @@ __global__ __launch_bounds__(kRowNT) void k_enc_rowA(KArgs a) {
         fetch_x(a, udesc(a.d, sn), tln, more, base1, nx);
         fix_x(a, D, tile, base1, v);
         const uint32_t b1 = seed_b(sld(a.seeds, D.tensor));
-        float ss = kLadFull ? sum_sq(v) : 1.0f;
-        if constexpr (kLadSign) apply_signs_direct<RS::L1>(v, tile << kRowLog, base1, D.logp, b1, 1.0f);
-        if constexpr (kLadFly) {
-            stages<RS::L1, RS::F1a>(v);
-            exchange<RS::L1, RS::L2>(v, s, tid);
-            stages<RS::L2, RS::F1b>(v);
-        }
-        if constexpr (kRowWs4) {
-            if constexpr (kLadFly) {
-                exchange<RS::L2, RS::L3F>(v, s, tid);
-                stages<RS::L3F, RS::F1c>(v);
-            }
-            store_ws4<RS::L3F>(a, D, tile, base3, v);
-        } else {
-            if constexpr (kLadFly) {
-                exchange<RS::L2, RS::L3>(v, s, tid);
-                stages<RS::L3, RS::F1c>(v);
-            }
-            store_ws(a, D, tile, base3, v);
-        }
-        if constexpr (kLadFull) ss = block_sum<kRowNT>(ss, red);
+        float ss = sum_sq(v);
+        apply_signs_direct<RS::L1>(v, tile << kRowLog, base1, D.logp, b1, 1.0f);
+        stages<RS::L1, RS::F1a>(v);
+        exchange<RS::L1, RS::L2>(v, s, tid);
+        stages<RS::L2, RS::F1b>(v);
+        exchange<RS::L2, RS::L3F>(v, s, tid);
+        stages<RS::L3F, RS::F1c>(v);
+        store_ws4<RS::L3F>(a, D, tile, base3, v);
+        ss = block_sum<kRowNT>(ss, red);
         if (tid == 0) a.part[D.part_off + tile] = ss;
-        if (!more) break;
-        t = tn; si = sn; tile = tln;
-    }
-}
-
-// encode pass C: ws -> F2 row stages -> y -> quantise, pack ; partial dot
-__global__ __launch_bounds__(kRowNT) void k_enc_rowC(KArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float* s = reinterpret_cast<float*>(smem);
-    float* red = reinterpret_cast<float*>(smem + kRowRed);
-    QTab* qt = reinterpret_cast<QTab*>(smem + kRowExtra);
-    const uint32_t tid = threadIdx.x;
-    load_qtable<kRowNT>(qt, a.nbits);
-    const TileWalk tw(a, reinterpret_cast<TileTab*>(smem + kRowTab), tid);  // its barrier publishes qt
-    int t = (int)blockIdx.x;
-    if (t >= tw.total) return;
-    const uint32_t base3 = LT<RS::L3>::base(tid), base5 = LT<RS::L5>::base(tid);
-    int si; uint32_t tile;
-    tw.at(t, si, tile);
-    float nx[64];
-    fetch_ws(a, udesc(a.d, si), tile, true, base3, nx);
-    for (;;) {
-        float v[64];
-#pragma unroll
-        for (int r = 0; r < 64; ++r) v[r] = nx[r];
-        const SliceDesc D = udesc(a.d, si);
-        const int tn = t + (int)gridDim.x;
-        const bool more = tn < tw.total;
-        int sn; uint32_t tln;
-        tw.at(more ? tn : t, sn, tln);
-        const SliceDesc Dn = udesc(a.d, sn);
-        fetch_ws(a, Dn, tln, more, base3, nx);
-        if constexpr (kLadFly) {
-            stages<RS::L3, RS::F2c>(v);
-            exchange<RS::L3, RS::L4>(v, s, tid);
-            stages<RS::L4, RS::F2d>(v);
-            exchange<RS::L4, RS::L5>(v, s, tid);
-            stages<RS::L5, RS::F2e>(v);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // keep the quantiser out of the butterflies (VGPR cap)
-        const float nu = sldf(a.nu, si);
-        const float ysc = pow2i(-((D.logp + 1) / 2));
-        const float zm64 = 64.0f * (sqrtf((float)(1ll << D.logp)) / nu);
-        uint64_t wd[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wd[i] = 0;
-        float dot = 1.0f;
-        if constexpr (kLadFull) {
-            dot = quant_pack64(v, ysc, zm64, qt, wd);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                wd[i] = (uint64_t)lad_word(v[8 * i], v[8 * i + 1], v[8 * i + 2], v[8 * i + 3]) |
-                        ((uint64_t)lad_word(v[8 * i + 4], v[8 * i + 5], v[8 * i + 6], v[8 * i + 7]) << 32);
-        }
-        if (!(nu > 0.0f)) {
-            dot = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) wd[i] = 0;
-        }
-        store_planes64(a.pout + D.pl_off, (tile << kRowLog) + base5, D.pl_stride, a.nbits, wd);
-        if constexpr (kLadFull) dot = block_sum<kRowNT>(dot, red);
-        if (tid == 0) a.part[D.part_off + tile] = dot;
         if (!more) break;
         t = tn; si = sn; tile = tln;
     }
@@ -1624,21 +1390,18 @@ __global__ __launch_bounds__(kRowNT) void k_dec_rowA(KArgs a) {
     fetch_planes<A8>(a, udesc(a.d, si), tile, true, base5, nw);
     for (;;) {
         float v[64];
-        if constexpr (kLadFull) unpack_centroids64(nw, cen, v);
-        else lad_unpack64(nw, v);
+        unpack_centroids64(nw, cen, v);
         const SliceDesc D = udesc(a.d, si);
         const int tn = t + (int)gridDim.x;
         const bool more = tn < tw.total;
         int sn; uint32_t tln;
         tw.at(more ? tn : t, sn, tln);
         fetch_planes<A8>(a, udesc(a.d, sn), tln, more, base5, nw);
-        if constexpr (kLadFly) {
-            stages<RS::L5, RS::F2e>(v);
-            exchange<RS::L5, RS::L4>(v, s, tid);
-            stages<RS::L4, RS::F2d>(v);
-            exchange<RS::L4, RS::L3>(v, s, tid);
-            stages<RS::L3, RS::F2c>(v);
-        }
+        stages<RS::L5, RS::F2e>(v);
+        exchange<RS::L5, RS::L4>(v, s, tid);
+        stages<RS::L4, RS::F2d>(v);
+        exchange<RS::L4, RS::L3>(v, s, tid);
+        stages<RS::L3, RS::F2c>(v);
         // (one more exchange to L3F for float4 stores: 494 -> 533 us per wave,
         // profiles/r03_deca_ws4_ab.txt)
         store_ws(a, D, tile, base3, v);
@@ -1655,12 +1418,11 @@ __global__ __launch_bounds__(kRowNT) void k_dec_rowC(KArgs a) {
     const TileWalk tw(a, reinterpret_cast<TileTab*>(smem + kRowTab), tid);
     int t = (int)blockIdx.x;
     if (t >= tw.total) return;
-    const uint32_t base1 = LT<RS::L1>::base(tid), base3 = LT<kRowWs4 ? RS::L3F : RS::L3>::base(tid);
+    const uint32_t base1 = LT<RS::L1>::base(tid), base3 = LT<RS::L3F>::base(tid);
     int si; uint32_t tile;
     tw.at(t, si, tile);
     float nx[64];
-    if constexpr (kRowWs4) fetch_ws4<RS::L3F>(a, udesc(a.d, si), tile, true, base3, nx);
-    else fetch_ws(a, udesc(a.d, si), tile, true, base3, nx);
+    fetch_ws4<RS::L3F>(a, udesc(a.d, si), tile, true, base3, nx);
     for (;;) {
         float v[64];
 #pragma unroll
@@ -1670,26 +1432,17 @@ __global__ __launch_bounds__(kRowNT) void k_dec_rowC(KArgs a) {
         const bool more = tn < tw.total;
         int sn; uint32_t tln;
         tw.at(more ? tn : t, sn, tln);
-        if constexpr (kRowWs4) fetch_ws4<RS::L3F>(a, udesc(a.d, sn), tln, more, base3, nx);
-        else fetch_ws(a, udesc(a.d, sn), tln, more, base3, nx);
+        fetch_ws4<RS::L3F>(a, udesc(a.d, sn), tln, more, base3, nx);
         const uint32_t b1 = seed_b(sld(a.seeds, D.tensor));
-        if constexpr (kLadFly) {
-            if constexpr (kRowWs4) {
-                stages<RS::L3F, RS::F1c>(v);
-                exchange<RS::L3F, RS::L2>(v, s, tid);
-            } else {
-                stages<RS::L3, RS::F1c>(v);
-                exchange<RS::L3, RS::L2>(v, s, tid);
-            }
-            stages<RS::L2, RS::F1b>(v);
-            exchange<RS::L2, RS::L1>(v, s, tid);
-            stages<RS::L1, RS::F1a>(v);
-        }
+        stages<RS::L3F, RS::F1c>(v);
+        exchange<RS::L3F, RS::L2>(v, s, tid);
+        stages<RS::L2, RS::F1b>(v);
+        exchange<RS::L2, RS::L1>(v, s, tid);
+        stages<RS::L1, RS::F1a>(v);
         // scale folded into the 2^-k normalisation: 2^-k is exact, so
         // v * (sc * 2^-k) rounds like (v * 2^-k) * sc (normal range)
         const float sc = sldf(a.scales_in, D.scale_idx);
-        if constexpr (kLadSign)
-            apply_signs_direct<RS::L1>(v, tile << kRowLog, base1, D.logp, b1, sc * pow2i(-((D.logp + 1) / 2)));
+        apply_signs_direct<RS::L1>(v, tile << kRowLog, base1, D.logp, b1, sc * pow2i(-((D.logp + 1) / 2)));
         store_y(a, D, tile, base1, v);
         if (!more) break;
         t = tn; si = sn; tile = tln;
@@ -1740,7 +1493,6 @@ DEVI void col_body(const KArgs& a, int b) {
     const uint32_t th = tile >> (lo - K);
     const uint32_t tb = (tl << K) | (th << (lo + M));
     float* w = a.ws + D.ws_off;
-    const int lgp = D.logp;
     auto map = [&](uint32_t t) -> uint32_t { return tb | (t & ((1u << K) - 1u)) | ((t >> K) << lo); };
     // sign-table index of tile element t: the tile bits below the nibble bits
     // (columns, then rows lo .. p-4), i.e. t with its top 3 bits removed
@@ -1753,7 +1505,7 @@ DEVI void col_body(const KArgs& a, int b) {
     float v[32];
     const uint32_t base1 = LT<CS::L1>::base(tid);
 #pragma unroll
-    for (int r = 0; r < 32; ++r) v[r] = ws_pld(w, lgp, map(base1 | LT<CS::L1>::off(r)));
+    for (int r = 0; r < 32; ++r) v[r] = w[map(base1 | LT<CS::L1>::off(r))];
     stages<CS::L1, CS::A1>(v);
     if constexpr (M > 5) {
         exchange<CS::L1, CS::L2>(v, s, tid);  // its barriers also publish tab
@@ -1791,16 +1543,16 @@ DEVI void col_body(const KArgs& a, int b) {
         }
         const uint32_t base1w = opaque(base1);
 #pragma unroll
-        for (int r = 0; r < 32; ++r) ws_pst<MID>(w, lgp, map(base1w | LT<CS::L1>::off(r)), v[r]);
+        for (int r = 0; r < 32; ++r) ws_pst<MID>(w, map(base1w | LT<CS::L1>::off(r)), v[r]);
     } else {
         if constexpr (M > 5) {
             const uint32_t base2 = opaque(LT<CS::L2>::base(tid));
 #pragma unroll
-            for (int r = 0; r < 32; ++r) ws_pst<MID>(w, lgp, map(base2 | LT<CS::L2>::off(r)), v[r]);
+            for (int r = 0; r < 32; ++r) ws_pst<MID>(w, map(base2 | LT<CS::L2>::off(r)), v[r]);
         } else {
             const uint32_t base1w = opaque(base1);
 #pragma unroll
-            for (int r = 0; r < 32; ++r) ws_pst<MID>(w, lgp, map(base1w | LT<CS::L1>::off(r)), v[r]);
+            for (int r = 0; r < 32; ++r) ws_pst<MID>(w, map(base1w | LT<CS::L1>::off(r)), v[r]);
         }
     }
     // The slice norm nu = sqrt(sum of the row pass's partials of x^2)
@@ -1892,13 +1644,12 @@ __global__ __launch_bounds__(kColNT) void k_dec_colm_set(KArgs a) {
 // Tile I/O through a buffer resource over the slice's intermediate: the row
 // part of every register's address is a scalar offset.
 // ===========================================================================
-// TL = log2 of the tile: 15 (512 threads, 2 blocks per CU) or 16 (1024
-// threads, one block per CU, twice the columns per row segment).
+// TL = log2 of the tile: 15 (512 threads, 2 blocks per CU).
 template <int TL> constexpr int col6_nt() { return 1 << (TL - 6); }
 template <int TL> constexpr size_t col6_half() { return sizeof(float) << (TL - 1); }
 template <int TL> constexpr size_t col6_tab() { return (size_t)1 << (TL - 3); }
 template <int M, int TL> struct Col6Set {
-    static_assert(M >= 6 && M <= 10 && (TL == 15 || TL == 16), "Col6Set: 6 <= M <= 10, TL 15 or 16");
+    static_assert(M >= 6 && M <= 10 && TL == 15, "Col6Set: 6 <= M <= 10, TL 15");
     static constexpr int K = TL - M;
     static constexpr int row2(int i) { return (M - 6 + i) + ((M - 6 + i) >= 5 ? 1 : 0); }  // i < 5
     static constexpr Lay L1{TL, K, K + 1, K + 2, K + 3, K + 4, K + 5};
@@ -1951,9 +1702,9 @@ __global__ __launch_bounds__(col6_nt<TL>(), 4) void k_col6(KArgs a) {
     const uint32_t th = tile >> (lo - K);
     const uint32_t tb = (tl << K) | (th << (lo + M));
     auto map = [&](uint32_t t) -> uint32_t { return tb | (t & ((1u << K) - 1u)) | ((t >> K) << lo); };
-    const WsR rw = ws_rsrc(a.ws + D.ws_off, D.logp, 0, (uint32_t)(4ull << D.logp));
+    const rsrc_t rw = mk_rsrc(a.ws + D.ws_off, (uint32_t)(4ull << D.logp));
     constexpr uint32_t kTabMask = (1u << (TL - 3)) - 1u;
-    if constexpr (MID && kLadSign) {  // D2 sign bytes of the tile's 2^12 rand_diag words (see k_col)
+    if constexpr (MID) {  // D2 sign bytes of the tile's 2^12 rand_diag words (see k_col)
         const uint32_t b2 = seed_b(sld(a.seeds, D.tensor) + 1u);
         for (uint32_t q = tid; q < (1u << (TL - 3)); q += NT)
             tab[q] = (uint8_t)rd_byte(map(q) & ((1u << (D.logp - 3)) - 1u), b2);
@@ -1978,8 +1729,8 @@ __global__ __launch_bounds__(col6_nt<TL>(), 4) void k_col6(KArgs a) {
         for (int r = 0; r < 64; ++r)
             v[r] = ws_ld1(rw, vo, uu((LT<CS::L1>::off(r) >> K) << lo) * 4u, kLd);
     }
-    if constexpr (kLadFly) stages<CS::L1, CS::A1>(v);
-    if constexpr (EXCH && kLadFly) {
+    stages<CS::L1, CS::A1>(v);
+    if constexpr (EXCH) {
         exchange_half<CS::L1, CS::L2, CS::HB>(v, s, tid);  // its barriers also publish tab
         stages<CS::L2, CS::A2>(v);
     } else if constexpr (MID) {
@@ -1992,18 +1743,16 @@ __global__ __launch_bounds__(col6_nt<TL>(), 4) void k_col6(KArgs a) {
         // immediate
         static_assert((LT<LC>::rmask() >> (TL - 3)) == 7u, "top 3 tile bits must be register bits");
         const uint32_t bt = opaque(LT<LC>::base(tid) & kTabMask);
-        if constexpr (kLadSign) {
 #pragma unroll
-            for (int r = 0; r < 64; ++r) {
-                const uint32_t o = LT<LC>::off(r);
-                v[r] = flip_unless(v[r] * m2, ((uint32_t)tab[bt + (o & kTabMask)] >> (o >> (TL - 3))) & 1u);
-            }
+        for (int r = 0; r < 64; ++r) {
+            const uint32_t o = LT<LC>::off(r);
+            v[r] = flip_unless(v[r] * m2, ((uint32_t)tab[bt + (o & kTabMask)] >> (o >> (TL - 3))) & 1u);
         }
-        if constexpr (EXCH && kLadFly) {
+        if constexpr (EXCH) {
             stages<CS::L2, CS::A2>(v);
             exchange_half<CS::L2, CS::L1, CS::HB>(v, s, tid);
         }
-        if constexpr (kLadFly) stages<CS::L1, CS::A1>(v);
+        stages<CS::L1, CS::A1>(v);
         if (perm) {
             const uint32_t vo = opaque(ws_pos(map(base1)) * 4u);
 #pragma unroll
@@ -2058,7 +1807,7 @@ DEVI void row_locate(const KArgs& a, int t, int& si, uint32_t& tile, uint32_t* p
 
 // ===========================================================================
 // Encode pass C with two blocks per CU (k_enc_rowC2).  The quantiser makes
-// k_enc_rowC latency-bound at one block per CU (LDS table reads, bank
+// the pass latency-bound at one block per CU (LDS table reads, bank
 // conflicts, barriers); here the F2 row stages run through layouts that all
 // keep element bit 10 at register index 5:
 //   L3 {5..10} (F2c) -> L4 {11..14,9,10} (F2d) -> L5 {0..4,10} (F2e),
@@ -2099,36 +1848,22 @@ template <int H, int AUX = kLdAux>
 DEVI void fetch_ws_half(const KArgs& a, const SliceDesc& D, uint32_t tile, bool live, uint32_t base3,
                         float (&v)[64]) {
     if (D.perm) {
-        const WsR r = ws_row(a, D, tile, live ? (4u << (kRowLog + 1)) - 128u : 0u);
+        const rsrc_t r = ws_row(a, D, tile, live ? (4u << (kRowLog + 1)) - 128u : 0u);
         const uint32_t b = ws_row_idx(base3);
 #pragma unroll
         for (int k = 32 * H; k < 32 * H + 32; ++k) v[k] = ws_ld1(r, b * 4u, (LT<RS::L3>::off(k) << 1) * 4u, AUX);
     } else {
-        const WsR r = ws_row(a, D, tile, live ? (4u << kRowLog) : 0u);
+        const rsrc_t r = ws_row(a, D, tile, live ? (4u << kRowLog) : 0u);
 #pragma unroll
         for (int k = 32 * H; k < 32 * H + 32; ++k) v[k] = ws_ld1(r, base3 * 4u, LT<RS::L3>::off(k) * 4u, AUX);
     }
 }
 
-// ROLL: the next tile's intermediate is loaded into the registers the
-// quantiser has just freed (its first half after the first 32-element run,
-// the second after the second), so the loads are in flight across the second
-// run, the plane stores and the dot reduction, with no extra registers (the
-// kernel sits at the 128-VGPR cap of two blocks per CU).
-// diagnostic builds only (-DOFL_DIAG_ROWC2=mask, wrong results, tools/ab):
-// 1 = no F2 exchanges, 2 = no quantiser, 4 = no dot reduction
-#ifndef OFL_DIAG_ROWC2
-#define OFL_DIAG_ROWC2 0
-#endif
-constexpr int kDiagRowC2 = OFL_DIAG_ROWC2;
-#ifndef OFL_ROWC2_LD_AUX
-#define OFL_ROWC2_LD_AUX 0
-#endif
-// the default policy since the arena I/O went nt (round 6: 478.5-479.2 vs
-// 476.7-478.7 GiB/s with nt, profiles/r06_rowc2ld_ab.txt; nt had won at the
-// 2 GiB waves of round 3, profiles/r03_nt_ab.txt)
-constexpr int kRowC2LdAux = OFL_ROWC2_LD_AUX;
-template <bool ROLL>
+// The next tile's intermediate is loaded into the registers the quantiser
+// has just freed (its first half after the first 32-element run, the second
+// after the second), so the loads are in flight across the second run, the
+// plane stores and the dot reduction, with no extra registers (the kernel
+// sits at the 128-VGPR cap of two blocks per CU).
 __global__ __launch_bounds__(kRowNT, 4) void k_enc_rowC2(KArgs a) {
     using R = RowC2Set;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2148,21 +1883,18 @@ __global__ __launch_bounds__(kRowNT, 4) void k_enc_rowC2(KArgs a) {
     float v[64];
     // the intermediate's last read: kRowC2LdAux (nt won at round 3's 2 GiB
     // waves, the default policy at round 6's MALL-sized ones)
-    if (ROLL) fetch_ws<kRowC2LdAux>(a, udesc(a.d, si), tile, true, base3, v);
+    fetch_ws<kRowC2LdAux>(a, udesc(a.d, si), tile, true, base3, v);
     for (;;) {
         const SliceDesc D = udesc(a.d, si);
         const int tn = t + (int)gridDim.x;
         const bool more = tn < total;
         int sn; uint32_t tln;
         locate(more ? tn : t, sn, tln);
-        if (!ROLL) fetch_ws<kRowC2LdAux>(a, D, tile, true, base3, v);
-        if constexpr (kLadFly) {
-            stages<R::L3, R::F2c>(v);
-            if (!(kDiagRowC2 & 1)) exchange_half_pad<R::L3, R::L4, R::HB>(v, s, tid);
-            stages<R::L4, R::F2d>(v);
-            if (!(kDiagRowC2 & 1)) exchange_half_pad<R::L4, R::L5, R::HB>(v, s, tid);
-            stages<R::L5, R::F2e>(v);
-        }
+        stages<R::L3, R::F2c>(v);
+        exchange_half_pad<R::L3, R::L4, R::HB>(v, s, tid);
+        stages<R::L4, R::F2d>(v);
+        exchange_half_pad<R::L4, R::L5, R::HB>(v, s, tid);
+        stages<R::L5, R::F2e>(v);
         __builtin_amdgcn_sched_barrier(0);
         const float nu = sldf(a.nu, si);
         const float ysc = pow2i(-((D.logp + 1) / 2));
@@ -2172,31 +1904,19 @@ __global__ __launch_bounds__(kRowNT, 4) void k_enc_rowC2(KArgs a) {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             uint32_t w[8];
-            if (!kLadFull) {  // ladder rungs: a plane word from 4 values, no quantiser
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    w[i] = lad_word(v[32 * g + 4 * i], v[32 * g + 4 * i + 1], v[32 * g + 4 * i + 2], v[32 * g + 4 * i + 3]);
-                dot = 1.0f;
-            } else if (kDiagRowC2 & 2) {  // diagnostic: no quantiser (wrong output)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) w[i] = __float_as_uint(v[32 * g + 4 * i]) ^ __float_as_uint(v[32 * g + 4 * i + 1]);
-                dot += v[32 * g];
-            } else {
-                dot += quant_pack32(*reinterpret_cast<const float(*)[32]>(&v[32 * g]), ysc, zm64, qt, w);
-            }
+            dot += quant_pack32(*reinterpret_cast<const float(*)[32]>(&v[32 * g]), ysc, zm64, qt, w);
             if (!pos) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) w[i] = 0;
             }
-            if (ROLL) {  // this half's registers are free: start the next tile's
-                if (g == 0) fetch_ws_half<0, kRowC2LdAux>(a, udesc(a.d, sn), tln, more, base3, v);
-                else fetch_ws_half<1, kRowC2LdAux>(a, udesc(a.d, sn), tln, more, base3, v);
-            }
+            // this half's registers are free: start the next tile's
+            if (g == 0) fetch_ws_half<0, kRowC2LdAux>(a, udesc(a.d, sn), tln, more, base3, v);
+            else fetch_ws_half<1, kRowC2LdAux>(a, udesc(a.d, sn), tln, more, base3, v);
             store_planes(a.pout + D.pl_off, (tile << kRowLog) + base5 + ((uint32_t)g << R::HB), D.pl_stride,
                          a.nbits, w);
         }
         if (!pos) dot = 0.f;
-        if (!(kDiagRowC2 & 4) && kLadFull) dot = block_sum<kRowNT>(dot, red);
+        dot = block_sum<kRowNT>(dot, red);
         if (tid == 0) a.part[D.part_off + tile] = dot;
         if (!more) break;
         t = tn; si = sn; tile = tln;
@@ -2224,7 +1944,7 @@ struct DecA2Set {  // decode pass A, half bit 5: 0..4 | 11,12,13,14,5 | 6..10
     static constexpr uint32_t G1 = RS::F2e, G2 = bits_mask({11, 12, 13, 14, 5}), G3 = bits_mask({6, 7, 8, 9, 10});
 };
 struct DecC2Set {  // decode pass C, half bit 10: 7,8,9 | 2..6,10 | 0,1,11,12,13 | 14
-    static constexpr Lay B1 = kRowWs4 ? RS::L3F : RS::L3, B2 = RS::L2, B3{15, 0, 1, 11, 12, 13, 10}, B4{15, 0, 1, 14, 11, 12, 10};
+    static constexpr Lay B1 = RS::L3F, B2 = RS::L2, B3{15, 0, 1, 11, 12, 13, 10}, B4{15, 0, 1, 14, 11, 12, 10};
     static constexpr uint32_t H1 = RS::F1c, H2 = RS::F1b, H3 = bits_mask({0, 1, 11, 12, 13}), H4 = bits_mask({14});
 };
 // apply_signs_direct in groups of 8 registers whose results are pinned before
@@ -2321,12 +2041,12 @@ constexpr size_t kRow2SmemC = kRowC2Ex + 1024;  // half-exchange buffer + 256 ce
 template <Lay L>
 DEVI void store_ws_l(const KArgs& a, const SliceDesc& D, uint32_t tile, uint32_t base, const float (&v)[64]) {
     if (D.perm) {
-        const WsR r = ws_row(a, D, tile, (4u << (kRowLog + 1)) - 128u);
+        const rsrc_t r = ws_row(a, D, tile, (4u << (kRowLog + 1)) - 128u);
         const uint32_t b = ws_row_idx(base);
 #pragma unroll
         for (int k = 0; k < 64; ++k) ws_st1(r, b * 4u, (LT<L>::off(k) << 1) * 4u, v[k], kStAux);
     } else {
-        const WsR r = ws_row(a, D, tile, 4u << kRowLog);
+        const rsrc_t r = ws_row(a, D, tile, 4u << kRowLog);
 #pragma unroll
         for (int k = 0; k < 64; ++k) ws_st1(r, base * 4u, LT<L>::off(k) * 4u, v[k], kStAux);
     }
@@ -2469,25 +2189,21 @@ __global__ __launch_bounds__(kRowNT, 4) void k_enc_rowA2(KArgs a) {
                              "+v"(v[r + 5]), "+v"(v[r + 6]), "+v"(v[r + 7]));
         }
         const uint32_t b1 = seed_b(sld(a.seeds, D.tensor));
-        float ss = kLadFull ? sum_sq(v) : 1.0f;
+        float ss = sum_sq(v);
         // the sum is taken here, not sunk past the sign flips (which would keep
         // the 64 unflipped values live through the butterflies and spill them)
         asm volatile("" : "+v"(ss));
-        if constexpr (kLadSign) {
-            if (!WAVG && pair)
-                apply_signs_pair<R::A1>(v, tile << kRowLog, base1, D.logp, b1, 1.0f, 1u + h, stash);
-            else
-                apply_signs_grouped<R::A1, !WAVG>(v, tile << kRowLog, base1, D.logp, b1, 1.0f);
-        }
-        if constexpr (kLadFly) {
-            stages<R::A1, R::F1a>(v);
-            exchange_half_pad<R::A1, R::A2, 14>(v, s, tid);
-            stages<R::A2, R::F1b>(v);
-            exchange_half_pad<R::A2, R::A3, 14>(v, s, tid);
-            stages<R::A3, R::F1c>(v);
-        }
+        if (!WAVG && pair)
+            apply_signs_pair<R::A1>(v, tile << kRowLog, base1, D.logp, b1, 1.0f, 1u + h, stash);
+        else
+            apply_signs_grouped<R::A1, !WAVG>(v, tile << kRowLog, base1, D.logp, b1, 1.0f);
+        stages<R::A1, R::F1a>(v);
+        exchange_half_pad<R::A1, R::A2, 14>(v, s, tid);
+        stages<R::A2, R::F1b>(v);
+        exchange_half_pad<R::A2, R::A3, 14>(v, s, tid);
+        stages<R::A3, R::F1c>(v);
         store_ws_l<R::A3>(a, D, tile, base3, v);
-        if constexpr (kLadFull) ss = block_sum<kRowNT>(ss, red);
+        ss = block_sum<kRowNT>(ss, red);
         if (tid == 0) a.part[D.part_off + tile] = ss;
         if (h >= pair) break;
       }
@@ -2513,15 +2229,12 @@ __global__ __launch_bounds__(kRowNT, 4) void k_dec_rowA2(KArgs a) {
         uint64_t w[8];
         fetch_planes<A8>(a, D, tile, true, base1, w);
         float v[64];
-        if constexpr (kLadFull) unpack_centroids64(w, cen, v);
-        else lad_unpack64(w, v);
-        if constexpr (kLadFly) {
-            stages<R::C1, R::G1>(v);
-            exchange_half_pad<R::C1, R::C2, 5>(v, s, tid);
-            stages<R::C2, R::G2>(v);
-            exchange_half_pad<R::C2, R::C3, 5>(v, s, tid);
-            stages<R::C3, R::G3>(v);
-        }
+        unpack_centroids64(w, cen, v);
+        stages<R::C1, R::G1>(v);
+        exchange_half_pad<R::C1, R::C2, 5>(v, s, tid);
+        stages<R::C2, R::G2>(v);
+        exchange_half_pad<R::C2, R::C3, 5>(v, s, tid);
+        stages<R::C3, R::G3>(v);
         store_ws_l<R::C3>(a, D, tile, base3, v);
     }
 }
@@ -2542,24 +2255,19 @@ __global__ __launch_bounds__(kRowNT, 4) void k_dec_rowC2(KArgs a) {
         const uint32_t base1 = LT<R::B1>::base(tid), base4 = LT<R::B4>::base(tid);
         const uint32_t tile = h ? tile0 + (1u << (D.logp - 18)) : tile0;
         float v[64];
-        if constexpr (kRowWs4) fetch_ws4<R::B1>(a, D, tile, true, base1, v, kDecC2LdAux);
-        else fetch_ws(a, D, tile, true, base1, v);
+        fetch_ws4<R::B1>(a, D, tile, true, base1, v, kDecC2LdAux);
         const uint32_t b1 = seed_b(sld(a.seeds, D.tensor));
-        if constexpr (kLadFly) {
-            stages<R::B1, R::H1>(v);
-            exchange_half_pad<R::B1, R::B2, 10>(v, s, tid);
-            stages<R::B2, R::H2>(v);
-            exchange_half_pad<R::B2, R::B3, 10>(v, s, tid);
-            stages<R::B3, R::H3>(v);
-            exchange_half_pad<R::B3, R::B4, 10>(v, s, tid);
-            stages<R::B4, R::H4>(v);
-        }
+        stages<R::B1, R::H1>(v);
+        exchange_half_pad<R::B1, R::B2, 10>(v, s, tid);
+        stages<R::B2, R::H2>(v);
+        exchange_half_pad<R::B2, R::B3, 10>(v, s, tid);
+        stages<R::B3, R::H3>(v);
+        exchange_half_pad<R::B3, R::B4, 10>(v, s, tid);
+        stages<R::B4, R::H4>(v);
         const float sc = sldf(a.scales_in, D.scale_idx);
-        if constexpr (kLadSign) {
-            const float mul = sc * pow2i(-((D.logp + 1) / 2));
-            if (pair) apply_signs_pair<R::B4>(v, tile << kRowLog, base4, D.logp, b1, mul, 1u + h, stash);
-            else apply_signs_grouped<R::B4>(v, tile << kRowLog, base4, D.logp, b1, mul);
-        }
+        const float mul = sc * pow2i(-((D.logp + 1) / 2));
+        if (pair) apply_signs_pair<R::B4>(v, tile << kRowLog, base4, D.logp, b1, mul, 1u + h, stash);
+        else apply_signs_grouped<R::B4>(v, tile << kRowLog, base4, D.logp, b1, mul);
         store_y_l<R::B4>(a, D, tile, base4, v);
         if (h >= pair) break;
       }
@@ -2615,9 +2323,8 @@ struct Launch {
     int count;       // list entries
     int64_t blocks;  // grid size
     int nu = 0;      // column: tile 0 of each slice writes the slice norm
-    int stream = 0;  // 0: the caller's stream, 1: the plan's side stream, 2 / 3: its small-slice streams
+    int stream = 0;  // 0: the caller's stream, 1: the plan's side stream, 2: its small-slice stream
     int join = 0;    // the caller's stream waits for the side stream before this launch
-    int tl = 15;     // column: log2 of the tile (16: k_col6 with 1024 threads)
     int btab_off = -1;  // column: per-block {slice, tile << 3 | group} table in ints
     int ptab_off = -1;  // row: the paired table {slice, tile << 3 | pair} in ints (npair entries)
     int npair = 0;
@@ -2655,8 +2362,8 @@ struct ofl_eden_plan {
     int nwaves = 0;
     int row2 = -1;              // row launches on the two-blocks-per-CU kernels: -1 auto, 0 never, 1 always
     int pair = -1;              // their tile pairs sharing D1 words: -1 auto, 0 never, 1 whenever possible
-    int sset = -1;              // tiny / small slices in one small-set launch: -1 env default, 0 no, 1 yes
-    int fuse = -1;              // small-set groups fused into the column launch: -1 env default, 0 no, 1 yes
+    int sset = -1;              // tiny / small slices in one small-set launch: -1 default (yes), 0 no, 1 yes
+    int fuse = -1;              // small-set groups fused into the column launch: -1 default (yes), 0 no, 1 yes
     bool single = false;        // every launch on the caller's stream (no fork / join) -- K_COLMSET plans
     std::vector<Launch> enc, dec;
     std::vector<int32_t> ints;  // launch lists and tile prefixes (host copy)
@@ -2672,8 +2379,7 @@ struct ofl_eden_plan {
     std::mutex mu;
     hipStream_t side = nullptr;  // nstreams == 2: the device's shared side streams (shared_side_streams)
     hipStream_t side2 = nullptr; // the tiny / small slices, beside both wave streams
-    hipStream_t side3 = nullptr; // half of the tiny / small launches (use_small_split)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_join3 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
     std::mutex run_mu;          // serialises runs that use the side stream
 };
 
@@ -2722,187 +2428,41 @@ hipError_t set_small_attr() {
 
 size_t col_smem(int M, bool mid) { return (M > 5 ? ofl::kColSmem : 0) + (mid && M >= 3 ? ofl::kColTab : 0); }
 
-template <int M>
-hipError_t set_col_attr() {
-    hipError_t e = set_lds((const void*)ofl::k_col<M, true>, col_smem(M, true));
-    return e != hipSuccess ? e : set_lds((const void*)ofl::k_col<M, false>, col_smem(M, false));
-}
+// k_col6 tiles are 2^15 elements, two blocks per CU (2^16-element tiles with
+// 1024 threads measured slower on the 2^24 / 2^25 middle passes: 457 vs 432
+// us, 357 vs 307 us per launch)
+size_t col6_smem(int M, bool mid) { return (M > 6 ? ofl::col6_half<15>() : 0) + (mid ? ofl::col6_tab<15>() : 0); }
 
-size_t col6_smem(int M, bool mid, int tl) {
-    return tl == 16 ? (M > 6 ? ofl::col6_half<16>() : 0) + (mid ? ofl::col6_tab<16>() : 0)
-                    : (M > 6 ? ofl::col6_half<15>() : 0) + (mid ? ofl::col6_tab<15>() : 0);
-}
-
-template <int M, int TL>
-hipError_t set_col6_attr() {
-    hipError_t e = set_lds((const void*)ofl::k_col6<M, true, TL>, col6_smem(M, true, TL));
-    return e != hipSuccess ? e : set_lds((const void*)ofl::k_col6<M, false, TL>, col6_smem(M, false, TL));
-}
-
-// 2^16-element tiles for the 2^24 / 2^25 middle column passes: off by default
-// (measured slower than two 2^15-tile blocks per CU: 457 vs 432 us, 357 vs
-// 307 us per launch); OFL_EDEN_COL16=1 selects them (A/B)
-bool use_col16() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_COL16"); return s && s[0] == '1'; }();
-    return on;
-}
-
-// encode pass C uses k_enc_rowC2 (OFL_EDEN_ROWC2=0: k_enc_rowC, A/B)
-bool use_rowc2() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_ROWC2"); return !(s && s[0] == '0'); }();
-    return on;
-}
-
-// k_enc_rowC2 loads the next tile into the quantiser's freed registers
-// (OFL_EDEN_ROLL=0: load at the top of each tile, A/B)
-bool use_roll() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_ROLL"); return !(s && s[0] == '0'); }();
-    return on;
-}
-
-// Row launches of fewer than row2_max_tiles_per_cu() tiles per CU use the
+// Row launches of fewer than kRow2MaxTilesPerCu tiles per CU use the
 // two-blocks-per-CU kernels (k_enc_rowA2 / k_dec_rowA2 / k_dec_rowC2; outputs
-// bit-identical).  OFL_EDEN_ROW2=0: never, =1: always, unset: below the
-// threshold (OFL_EDEN_ROW2_TPC tiles per CU, default 5).
-int row2_mode() {
-    static const int m = [] { const char* s = getenv("OFL_EDEN_ROW2"); return (s && *s) ? (s[0] == '1' ? 1 : 0) : -1; }();
-    return m;
-}
-int64_t row2_max_tiles_per_cu() {
-    static const int64_t v = [] { const char* s = getenv("OFL_EDEN_ROW2_TPC"); return (s && *s) ? strtoll(s, nullptr, 10) : 5ll; }();
-    return v;
-}
+// bit-identical).  plan_mode (ofl_eden_plan_set_row2) 0: never, 1: always,
+// -1: below the threshold.
+constexpr int64_t kRow2MaxTilesPerCu = 5;
 bool use_row2(int64_t tiles, int ncu, int plan_mode) {
-    const int m = plan_mode >= 0 ? plan_mode : row2_mode();
-    return m >= 0 ? m == 1 : tiles < row2_max_tiles_per_cu() * (int64_t)ncu;
+    return plan_mode >= 0 ? plan_mode == 1 : tiles < kRow2MaxTilesPerCu * (int64_t)ncu;
 }
 
-// column passes with M >= 8 rows, or a middle pass with M >= 6, use k_col6
-// (measured: the 1024-thread k_col is ~4 % faster on the plain M = 7 pass);
-// OFL_EDEN_COL6=0 forces k_col everywhere (A/B)
-bool use_col6() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_COL6"); return !(s && s[0] == '0'); }();
-    return on;
-}
-// lowest outer (non-middle) column-pass height that runs k_col6
-// (OFL_EDEN_COL6_OUTER, default 8: the 5-pass slices' level-1 passes of
-// heights 5..7 run k_col)
-int col6_outer_min() {
-    static const int v = [] { const char* s = getenv("OFL_EDEN_COL6_OUTER"); return (s && *s) ? atoi(s) : 8; }();
-    return v;
-}
-// interleaved ws layout for 2^25 slices (256-B segments in the middle pass)
-bool use_perm25() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_PERM25"); return !(s && s[0] == '0'); }();
-    return on;
-}
-// the tiny / small launches (latency-bound, independent of each other) split
-// over two streams instead of one (OFL_EDEN_SMALL2=0: one stream, A/B)
-// (opt-in OFL_EDEN_SMALL2=1: measured slower on ResNet-50, 259-269 vs
-// 273-276 GiB/s, profiles/r03_resnet50_row2_small2_ab.txt)
-bool use_small_split() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_SMALL2"); return s && s[0] == '1'; }();
-    return on;
-}
-// every tiny / small slice in one small-set launch (k_enc_sset / k_dec_sset)
-// instead of a chain of one launch per size class (OFL_EDEN_SSET=0, A/B)
-bool use_sset() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_SSET"); return !(s && s[0] == '0'); }();
-    return on;
-}
-// tiny / small slices on a third stream when the waves use two
-bool use_small_stream() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_SMALLSTREAM"); return !(s && s[0] == '0'); }();
-    return on;
-}
-// two-stream plans whose large slices fit one wave split them into exactly
-// two balanced waves (OFL_EDEN_TWOWAVES=0: in-order packing against half the
-// total)
-bool use_two_waves() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_TWOWAVES"); return !(s && s[0] == '0'); }();
-    return on;
-}
-// the whole-slice middle pass of a split 5-pass slice streams its
-// intermediate with nt loads and stores (OFL_EDEN_MIDNT=0: default policy)
-bool use_mid_nt() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_MIDNT"); return !(s && s[0] == '0'); }();
-    return on;
-}
-int64_t big_sub_mib() {
-    static const int64_t v = [] { const char* s = getenv("OFL_EDEN_BIGSUB_MIB"); return (s && *s) ? strtoll(s, nullptr, 10) : 0ll; }();
-    return v;
-}
-// 5-pass slices bigger than a wave run their first two and last two passes
-// in MALL-sized sub-waves (OFL_EDEN_BIGSPLIT=0: whole-slice passes)
-bool use_big_split() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_BIGSPLIT"); return !(s && s[0] == '0'); }();
-    return on;
-}
-// multi-wave plans pack their large slices largest first (OFL_EDEN_WAVESORT=0:
-// in batch order, =2: smallest first; profiles/r06_sort_roll_ab.txt)
-int wave_sort_mode() {
-    static const int m = [] { const char* s = getenv("OFL_EDEN_WAVESORT"); return (s && *s) ? (int)(s[0] - '0') : 1; }();
-    return m;
-}
-bool use_wave_sort() { return wave_sort_mode() != 0; }
-// column launches find their tile in a per-block table (OFL_EDEN_BTAB=0:
-// binary search over the launch's tile prefix, as before)
-bool use_btab() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_BTAB"); return !(s && s[0] == '0'); }();
-    return on;
-}
 // row launches up to this many tiles carry a per-tile table (8 B per tile)
 constexpr int64_t kRowTabMax = 1 << 16;
 // two-blocks-per-CU row launches of more tiles than block slots run tile
-// pairs sharing their D1 words (apply_signs_pair; OFL_EDEN_PAIR=0: never,
-// =1: whenever the launch has a paired table)
-int pair_mode() {
-    static const int m = [] { const char* s = getenv("OFL_EDEN_PAIR"); return (s && *s) ? (s[0] == '1' ? 1 : 0) : -1; }();
-    return m;
-}
+// pairs sharing their D1 words (apply_signs_pair; plan_mode, see
+// ofl_eden_plan_set_pair, 0: never, 1: whenever the launch has a paired table)
 bool use_pair(const Launch& l, int ncu, int plan_mode) {
-    if (l.ptab_off < 0 || !use_btab()) return false;
-    const int m = plan_mode >= 0 ? plan_mode : pair_mode();
-    return m >= 0 ? m == 1 : l.blocks > 2 * (int64_t)ncu;
+    if (l.ptab_off < 0) return false;
+    return plan_mode >= 0 ? plan_mode == 1 : l.blocks > 2 * (int64_t)ncu;
 }
-// OFL_EDEN_SPLIT_MIB=m: two-stream plans split their large slices into two
-// waves only above m MiB of intermediates; unset (-1): see build_schedule
-int64_t split_min_bytes() {
-    static const int64_t b = [] {
-        const char* s = getenv("OFL_EDEN_SPLIT_MIB");
-        const int64_t m = (s && *s) ? strtoll(s, nullptr, 10) : -1;
-        return m < 0 ? -1 : m << 20;
-    }();
-    return b;
-}
-// one-wave plans with a k_col_multi launch and a small-set launch fuse the
-// two into one launch on the caller's stream (OFL_EDEN_FUSESET=0: the
-// small-set launch beside the wave on the side stream)
-bool use_fuse_sset() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_FUSESET"); return !(s && s[0] == '0'); }();
-    return on;
-}
-// height-6 middle passes (2^21 slices) run col_body<6> (1024 threads, the
-// k_col arithmetic) and join the k_col_multi launch of the smaller heights;
-// OFL_EDEN_COLM6=0: their own k_col6<6, true, 15> launch after it (A/B; the
-// two differ in the order of the row butterflies after D2, so their bytes
-// differ slightly -- every schedule of one setting is bit-identical)
-bool use_colm6() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_COLM6"); return !(s && s[0] == '0'); }();
-    return on;
-}
-// lowest middle-pass height that runs k_col6 (7 when height 6 runs col_body<6>:
-// a standalone height-6 launch then uses k_col<6, true> too)
-int col6_mid_min() { return use_colm6() ? 7 : 6; }
-// k_col6 (else k_col) for a column pass of this height
-bool col6_for(int param, bool mid) {
-    return (param >= 8 || (mid ? param >= col6_mid_min() : param >= col6_outer_min())) && param >= 6 && use_col6();
-}
-// one k_col_multi launch per wave for the single-level heights 1..5 (6)
-bool use_colmulti() {
-    static const bool on = [] { const char* s = getenv("OFL_EDEN_COLMULTI"); return !(s && s[0] == '0'); }();
-    return on;
-}
+
+// Single-level heights up to kColMultiMax share one k_col_multi launch per
+// wave.  Height 6 (2^21 slices) runs col_body<6> there (1024 threads, the
+// k_col arithmetic), not k_col6<6, true, 15>: the two differ in the order of
+// the row butterflies after D2, so their bytes differ slightly, and a
+// standalone height-6 launch uses k_col<6, true> too.
+constexpr int kColMultiMax = 6;
+// k_col6 (else k_col) for a column pass of this height: middle passes above
+// kColMultiMax, outer passes from 8 (measured: the 1024-thread k_col is ~4 %
+// faster on the plain M = 7 pass; the 5-pass slices' level-1 passes of heights
+// 5..7 run k_col)
+bool col6_for(int param, bool mid) { return param >= (mid ? kColMultiMax + 1 : 8); }
 
 // What a row launch (K_ROWA / K_ROWC) runs -- decided here alone, for run()
 // and for the names and details the plan reports (launch_name,
@@ -2927,8 +2487,9 @@ RowChoice row_choice(const ofl_eden_plan* pl, const Launch& l, bool enc, bool wa
         c.grid = std::min<int64_t>(c.npair, 2 * pl->ncu);
         return c;
     }
+    // encode pass C has the two-blocks-per-CU kernel only (k_enc_rowC2)
     if (l.kind == K_ROWA ? wavg || use_row2(l.blocks, pl->ncu, pl->row2)
-                         : (enc ? use_rowc2() : use_row2(l.blocks, pl->ncu, pl->row2))) {
+                         : enc || use_row2(l.blocks, pl->ncu, pl->row2)) {
         c.two = true;
         c.grid = std::min<int64_t>(l.blocks, 2 * pl->ncu);
         if (signs && !wavg && use_pair(l, pl->ncu, pl->pair)) {
@@ -2942,10 +2503,9 @@ RowChoice row_choice(const ofl_eden_plan* pl, const Launch& l, bool enc, bool wa
 }
 
 // the kernel of a column launch (K_COL), for run() and launch_name
-enum ColKernel { COL_PLAIN, COL6, COL6_NT, COL6_TL16 };
+enum ColKernel { COL_PLAIN, COL6, COL6_NT };
 ColKernel col_choice(const Launch& l) {
-    if (l.tl == 16) return COL6_TL16;
-    if (l.nt && l.param == 7 && l.mid && col6_for(7, true)) return COL6_NT;
+    if (l.nt && l.param == 7 && l.mid) return COL6_NT;
     return col6_for(l.param, l.mid != 0) ? COL6 : COL_PLAIN;
 }
 
@@ -2962,9 +2522,7 @@ hipError_t set_all_attrs() {
     if ((e = set_lds((const void*)ofl::k_dec_colm_set, std::max(ofl::kSetSmemDec, ofl::kColMultiSmem))) != hipSuccess) return e;
     if ((e = set_lds((const void*)ofl::k_col_multi, ofl::kColMultiSmem)) != hipSuccess) return e;
     if ((e = set_lds((const void*)ofl::k_enc_rowA, ofl::kRowSmemA)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_enc_rowC, ofl::kRowSmemQ)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_enc_rowC2<true>, ofl::kRowC2Smem)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_enc_rowC2<false>, ofl::kRowC2Smem)) != hipSuccess) return e;
+    if ((e = set_lds((const void*)ofl::k_enc_rowC2, ofl::kRowC2Smem)) != hipSuccess) return e;
     if ((e = set_lds((const void*)ofl::k_dec_rowA<true>, ofl::kRowSmemC)) != hipSuccess) return e;
     if ((e = set_lds((const void*)ofl::k_dec_rowA<false>, ofl::kRowSmemC)) != hipSuccess) return e;
     if ((e = set_lds((const void*)ofl::k_dec_rowC, ofl::kRowSmemA)) != hipSuccess) return e;
@@ -2973,19 +2531,15 @@ hipError_t set_all_attrs() {
     if ((e = set_lds((const void*)ofl::k_dec_rowA2<true>, ofl::kRow2SmemC)) != hipSuccess) return e;
     if ((e = set_lds((const void*)ofl::k_dec_rowA2<false>, ofl::kRow2SmemC)) != hipSuccess) return e;
     if ((e = set_lds((const void*)ofl::k_dec_rowC2, ofl::kRow2Smem)) != hipSuccess) return e;
-    if ((e = set_col_attr<6>()) != hipSuccess) return e;
-    if ((e = set_col_attr<7>()) != hipSuccess) return e;
-    if ((e = set_col_attr<8>()) != hipSuccess) return e;
-    if ((e = set_col_attr<9>()) != hipSuccess) return e;
-    if ((e = set_col_attr<10>()) != hipSuccess) return e;
-    if ((e = set_col6_attr<6, 15>()) != hipSuccess) return e;
-    if ((e = set_col6_attr<7, 15>()) != hipSuccess) return e;
-    if ((e = set_col6_attr<8, 15>()) != hipSuccess) return e;
-    if ((e = set_col6_attr<9, 15>()) != hipSuccess) return e;
-    if ((e = set_col6_attr<10, 15>()) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_col6<7, true, 15, true>, col6_smem(7, true, 15))) != hipSuccess) return e;
-    if ((e = set_col6_attr<9, 16>()) != hipSuccess) return e;
-    return set_col6_attr<10, 16>();
+    // the column kernels a plan can launch (run(), K_COL) that exchange through LDS
+    if ((e = set_lds((const void*)ofl::k_col<6, true>, col_smem(6, true))) != hipSuccess) return e;
+    if ((e = set_lds((const void*)ofl::k_col<6, false>, col_smem(6, false))) != hipSuccess) return e;
+    if ((e = set_lds((const void*)ofl::k_col<7, false>, col_smem(7, false))) != hipSuccess) return e;
+    if ((e = set_lds((const void*)ofl::k_col6<7, true, 15>, col6_smem(7, true))) != hipSuccess) return e;
+    if ((e = set_lds((const void*)ofl::k_col6<8, true, 15>, col6_smem(8, true))) != hipSuccess) return e;
+    if ((e = set_lds((const void*)ofl::k_col6<9, true, 15>, col6_smem(9, true))) != hipSuccess) return e;
+    if ((e = set_lds((const void*)ofl::k_col6<10, true, 15>, col6_smem(10, true))) != hipSuccess) return e;
+    return set_lds((const void*)ofl::k_col6<7, true, 15, true>, col6_smem(7, true));
 }
 
 int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller) {
@@ -3000,10 +2554,8 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
         HIP_TRY(hipEventRecord(pl->ev_fork, caller));
         HIP_TRY(hipStreamWaitEvent(pl->side, pl->ev_fork, 0));
         if (pl->side2) HIP_TRY(hipStreamWaitEvent(pl->side2, pl->ev_fork, 0));
-        if (pl->side3) HIP_TRY(hipStreamWaitEvent(pl->side3, pl->ev_fork, 0));
     }
-    const hipStream_t streams[4] = {caller, two ? pl->side : caller, pl->side2 ? pl->side2 : caller,
-                                    pl->side3 ? pl->side3 : (pl->side2 ? pl->side2 : caller)};
+    const hipStream_t streams[3] = {caller, two ? pl->side : caller, pl->side2 ? pl->side2 : caller};
     bool joined = !two;
     std::vector<hipEvent_t>* evs = nullptr;
     if (pl->prof) {  // one event before and one after every launch, on its stream
@@ -3028,7 +2580,7 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
         ofl::KArgs a = base;
         a.list = pl->d_ints + l.list_off;
         a.tstart = l.tstart_off >= 0 ? pl->d_ints + l.tstart_off : nullptr;
-        a.btab = l.btab_off >= 0 && use_btab() ? pl->d_ints + l.btab_off : nullptr;
+        a.btab = l.btab_off >= 0 ? pl->d_ints + l.btab_off : nullptr;
         a.count = l.count;
         a.lo = l.lo;
         a.do_nu = l.nu;
@@ -3080,53 +2632,46 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
             const RowChoice rc = row_choice(pl, l, enc, false);
             if (rc.tab_off >= 0) a.btab = pl->d_ints + rc.tab_off;
             a.npair = rc.npair;
-            if (rc.two)
-                e = !enc ? launch(ofl::k_dec_rowC2, rc.grid, ofl::kRowNT, ofl::kRow2Smem, st, a)
-                    : use_roll() ? launch(ofl::k_enc_rowC2<true>, rc.grid, ofl::kRowNT, ofl::kRowC2Smem, st, a)
-                                 : launch(ofl::k_enc_rowC2<false>, rc.grid, ofl::kRowNT, ofl::kRowC2Smem, st, a);
+            if (enc)  // always two blocks per CU (row_choice)
+                e = launch(ofl::k_enc_rowC2, rc.grid, ofl::kRowNT, ofl::kRowC2Smem, st, a);
             else
-                e = enc ? launch(ofl::k_enc_rowC, rc.grid, ofl::kRowNT, ofl::kRowSmemQ, st, a)
-                        : launch(ofl::k_dec_rowC, rc.grid, ofl::kRowNT, ofl::kRowSmemA, st, a);
+                e = rc.two ? launch(ofl::k_dec_rowC2, rc.grid, ofl::kRowNT, ofl::kRow2Smem, st, a)
+                           : launch(ofl::k_dec_rowC, rc.grid, ofl::kRowNT, ofl::kRowSmemA, st, a);
             break;
         }
         case K_COL: {
             const ColKernel ck = col_choice(l);
-            if (ck == COL6_TL16) {  // 2^16-element tiles (M = 9, 10)
-                const size_t sm = col6_smem(l.param, l.mid != 0, 16);
-                e = l.param == 9 ? (l.mid ? launch(ofl::k_col6<9, true, 16>, l.blocks, 1024, sm, st, a)
-                                          : launch(ofl::k_col6<9, false, 16>, l.blocks, 1024, sm, st, a))
-                                 : (l.mid ? launch(ofl::k_col6<10, true, 16>, l.blocks, 1024, sm, st, a)
-                                          : launch(ofl::k_col6<10, false, 16>, l.blocks, 1024, sm, st, a));
-                break;
-            }
+            // build_schedule makes middle passes of heights 1..10 (k_col to
+            // 6, k_col6 above) and outer passes, the level-1 halves of the
+            // two-level slices 2^26..2^29, of heights 5..7 (k_col)
             if (ck == COL6_NT) {
-                e = launch(ofl::k_col6<7, true, 15, true>, l.blocks, 512, col6_smem(7, true, 15), st, a);
+                e = launch(ofl::k_col6<7, true, 15, true>, l.blocks, 512, col6_smem(7, true), st, a);
                 break;
             }
             if (ck == COL6) {
-                const size_t sm = col6_smem(l.param, l.mid != 0, 15);
-#define COL6CASE(MM)                                                                                 \
-    case MM:                                                                                         \
-        e = l.mid ? launch(ofl::k_col6<MM, true, 15>, l.blocks, 512, sm, st, a)                      \
-                  : launch(ofl::k_col6<MM, false, 15>, l.blocks, 512, sm, st, a);                    \
-        break;
-                switch (l.param) {
-                    COL6CASE(6) COL6CASE(7) COL6CASE(8) COL6CASE(9) COL6CASE(10)
+                const size_t sm = col6_smem(l.param, l.mid != 0);
+#define COL6CASE(MM) \
+    case MM: e = launch(ofl::k_col6<MM, true, 15>, l.blocks, 512, sm, st, a); break;
+                switch (l.mid ? l.param : 0) {
+                    COL6CASE(7) COL6CASE(8) COL6CASE(9) COL6CASE(10)
                 default: return fail(OFL_EINVAL, "column pass height out of range");
                 }
 #undef COL6CASE
                 break;
             }
             const size_t sm = col_smem(l.param, l.mid != 0);
-#define COLCASE(MM)                                                                                  \
-    case MM:                                                                                         \
-        e = l.mid ? launch(ofl::k_col<MM, true>, l.blocks, ofl::kColNT, sm, st, a)                   \
-                  : launch(ofl::k_col<MM, false>, l.blocks, ofl::kColNT, sm, st, a);                 \
-        break;
-            switch (l.param) {
-                COLCASE(1) COLCASE(2) COLCASE(3) COLCASE(4) COLCASE(5) COLCASE(6) COLCASE(7) COLCASE(8) COLCASE(9)
-                COLCASE(10)
-            default: return fail(OFL_EINVAL, "column pass height out of range");
+#define COLCASE(MM, MIDV) \
+    case MM: e = launch(ofl::k_col<MM, MIDV>, l.blocks, ofl::kColNT, sm, st, a); break;
+            if (l.mid) {
+                switch (l.param) {
+                    COLCASE(1, true) COLCASE(2, true) COLCASE(3, true) COLCASE(4, true) COLCASE(5, true) COLCASE(6, true)
+                default: return fail(OFL_EINVAL, "column pass height out of range");
+                }
+            } else {
+                switch (l.param) {
+                    COLCASE(5, false) COLCASE(6, false) COLCASE(7, false)
+                default: return fail(OFL_EINVAL, "column pass height out of range");
+                }
             }
 #undef COLCASE
             break;
@@ -3151,10 +2696,6 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
         HIP_TRY(hipEventRecord(pl->ev_join2, pl->side2));
         HIP_TRY(hipStreamWaitEvent(caller, pl->ev_join2, 0));
     }
-    if (two && pl->side3) {
-        HIP_TRY(hipEventRecord(pl->ev_join3, pl->side3));
-        HIP_TRY(hipStreamWaitEvent(caller, pl->ev_join3, 0));
-    }
     return OFL_OK;
 }
 
@@ -3165,14 +2706,10 @@ std::string launch_name(const ofl_eden_plan* pl, const Launch& l, bool enc) {
     case K_SSET: return std::string("ofl::k_") + d + "_sset";
     case K_SMALL: return std::string("ofl::k_") + d + "_small<" + std::to_string(l.param) + ">";
     case K_ROWA: return std::string("ofl::k_") + d + (row_choice(pl, l, enc, false).two ? "_rowA2" : "_rowA");
-    case K_ROWC:
-        if (!row_choice(pl, l, enc, false).two) return std::string("ofl::k_") + d + "_rowC";
-        if (enc) return std::string("ofl::k_enc_rowC2<") + (use_roll() ? "true" : "false") + ">";
-        return "ofl::k_dec_rowC2";
+    case K_ROWC: return std::string("ofl::k_") + d + (row_choice(pl, l, enc, false).two ? "_rowC2" : "_rowC");
     case K_COL: {
         const std::string mp = std::to_string(l.param) + ", " + (l.mid ? "true" : "false");
         switch (col_choice(l)) {
-        case COL6_TL16: return "ofl::k_col6<" + mp + ", 16>";
         case COL6_NT: return "ofl::k_col6<" + mp + ", 15, true>";
         case COL6: return "ofl::k_col6<" + mp + ", 15>";
         default: return "ofl::k_col<" + mp + ">";
@@ -3209,7 +2746,7 @@ void build_schedule(ofl_eden_plan* pl) {
         return o;
     };
     std::vector<Launch> common;
-    const bool sset = pl->sset >= 0 ? pl->sset == 1 : use_sset();
+    const bool sset = pl->sset != 0;
     if (sset) {
         // one small-set launch: groups of one size, largest first; table of
         // {P (0: tiny), slice-list offset (from the table), count} per block
@@ -3250,35 +2787,33 @@ void build_schedule(ofl_eden_plan* pl) {
     for (int32_t si : pl->large) tot += 1ll << pl->slices[si].logp;
     // more than one wave by size: the large slices largest first (stable), so
     // in-order packing fills each wave with slices of one size -- power-of-two
-    // sizes pack whole waves, one column launch per wave (OFL_EDEN_WAVESORT).
+    // sizes pack whole waves, one column launch per wave (batch order and
+    // smallest first both lost, profiles/r06_sort_roll_ab.txt).
     // Llama-3-8B: 210 waves of 1024 tiles (but the two 2^29 ones), 637
     // launches per direction instead of 258 waves of 512-1024 tiles and 909
     // launches; 434.8-435.4 -> 445.7-448.8 GiB/s
     std::vector<int32_t> sorted_large;
-    if (tot > cap && use_wave_sort()) {
+    if (tot > cap) {
         sorted_large = pl->large;
-        const bool up = wave_sort_mode() == 2;
-        std::stable_sort(sorted_large.begin(), sorted_large.end(), [&](int32_t x, int32_t y) {
-            return up ? pl->slices[x].logp < pl->slices[y].logp : pl->slices[x].logp > pl->slices[y].logp;
-        });
+        std::stable_sort(sorted_large.begin(), sorted_large.end(),
+                         [&](int32_t x, int32_t y) { return pl->slices[x].logp > pl->slices[y].logp; });
     }
     const std::vector<int32_t>& large = sorted_large.empty() ? pl->large : sorted_large;
     // two streams: at least two waves, so both streams have work -- unless
     // every large slice fits one wave and no small-slice launches could use
     // the second stream (at 2 GiB waves the 1 GiB set ran one wave on one
     // stream, 2.24 vs 2.29 ms; ResNet-50 keeps its two waves beside the small slices: 360
-    // vs 369 us with one wave; OFL_EDEN_SPLIT_MIB=m splits above m MiB)
+    // vs 369 us with one wave)
     // With the small-set launch a plan that fits one wave keeps it whole: the
     // one small-set launch runs beside it on the side stream (ResNet-50 0.288
     // vs 0.309 ms with two waves, profiles/r03_resnet50_sset_onewave_ab.txt)
-    const int64_t split_min = split_min_bytes();
-    const bool split = split_min >= 0 ? 4 * tot > split_min : ((!common.empty() && !sset) || tot > cap);
+    const bool split = (!common.empty() && !sset) || tot > cap;
     // the split only feeds the second stream (everything fits one wave):
     // exactly two waves, cut where the halves are closest (in-order packing
     // against a half-total cap can leave a third wave behind the first on the
     // same stream -- ResNet-50: 417 vs 353 tiles per stream)
     int64_t cut = -1;
-    if (pl->nstreams == 2 && split && tot <= cap && large.size() > 1 && use_two_waves()) {
+    if (pl->nstreams == 2 && split && tot <= cap && large.size() > 1) {
         int64_t pre = 0, best = INT64_MAX;
         for (size_t k = 0; k + 1 < large.size(); ++k) {
             pre += 1ll << pl->slices[large[k]].logp;
@@ -3300,21 +2835,14 @@ void build_schedule(ofl_eden_plan* pl) {
     pl->nwaves = (int)waves.size();
     const int nbuf = waves.size() > 1 ? pl->nstreams : 1;
     // the tiny / small slices are independent of the waves: with two wave
-    // streams they get a third (or, OFL_EDEN_SMALLSTREAM=0, the wave stream
-    // with fewer large-slice elements)
+    // streams they get a third (latency-bound, they fill CUs beside both
+    // waves; splitting them over two streams measured slower on ResNet-50,
+    // 259-269 vs 273-276 GiB/s, profiles/r03_resnet50_row2_small2_ab.txt)
     bool small_own = false;
     if (nbuf == 2) {
-        if (use_small_stream()) {  // their own stream(s): latency-bound, they fill CUs beside both waves
-            int k = 0;
-            for (Launch& l : common) l.stream = use_small_split() && common.size() > 1 ? 2 + (k++ & 1) : 2;
-            small_own = true;
-        } else {
-            int64_t load[2] = {0, 0};
-            for (size_t w = 0; w < waves.size(); ++w)
-                for (int32_t si : waves[w]) load[w % 2] += 1ll << pl->slices[si].logp;
-            for (Launch& l : common) l.stream = load[1] < load[0] ? 1 : 0;
-        }
-    } else if (pl->nstreams == 2 && !waves.empty() && use_small_stream()) {
+        for (Launch& l : common) l.stream = 2;
+        small_own = true;
+    } else if (pl->nstreams == 2 && !waves.empty()) {
         // one wave (too few tiles to split): the small slices run beside it
         // on the side stream
         for (Launch& l : common) l.stream = 1;
@@ -3336,13 +2864,12 @@ void build_schedule(ofl_eden_plan* pl) {
     for (int32_t si : large) a8 &= (pl->slices[si].pl_off % 8 == 0) && (pl->slices[si].pl_stride % 8 == 0);
     // one wave with a k_col_multi launch and one small-set launch: fused
     // (k_*_colm_set), everything on the caller's stream
-    const int mmax = use_colm6() ? 6 : 5;
     bool fuse = false;
-    if ((pl->fuse >= 0 ? pl->fuse == 1 : use_fuse_sset()) && use_colmulti() && waves.size() == 1 && common.size() == 1 && common[0].kind == K_SSET) {
+    if (pl->fuse != 0 && waves.size() == 1 && common.size() == 1 && common[0].kind == K_SSET) {
         std::set<int> hs;
         for (int32_t si : waves[0]) {
             const int r = pl->slices[si].logp - ofl::kRowLog;
-            if (r >= 1 && r <= mmax) hs.insert(r);
+            if (r >= 1 && r <= kColMultiMax) hs.insert(r);
         }
         fuse = hs.size() >= 2;  // the condition for the k_col_multi launch below
     }
@@ -3367,17 +2894,14 @@ void build_schedule(ofl_eden_plan* pl) {
         // middle pass (column level 2 + D2) spans the slice and runs whole,
         // writing the slice norm (it follows every row-A sub-wave).  Launches
         // of one stream run in order, so no other synchronisation.
-        if (wl.size() == 1 && cap != INT64_MAX && use_big_split() && use_rowc2() && use_btab() &&
-            pl->slices[wl[0]].logp - ofl::kRowLog >= 11) {
+        if (wl.size() == 1 && cap != INT64_MAX && pl->slices[wl[0]].logp - ofl::kRowLog >= 11) {
             const int32_t si = wl[0];
             const int p = pl->slices[si].logp, r = p - ofl::kRowLog, m1 = r / 2, m2 = r - m1;
             const int64_t ntile = 1ll << r, sub = 1ll << m1, P = 1ll << (p - 18);
             const int64_t cap_t = cap >> ofl::kRowLog;
-            // sub-wave size: the wave size (OFL_EDEN_BIGSUB_MIB overrides, A/B)
-            const int64_t sw_t = big_sub_mib() > 0 ? (big_sub_mib() << 20) / 4 >> ofl::kRowLog : cap_t;
-            const int64_t half = (sw_t / 2) / sub * sub;
+            const int64_t half = (cap_t / 2) / sub * sub;  // sub-wave size: the wave size
             if (half >= sub && cap_t < ntile && ntile <= kRowTabMax && use_row2(2 * std::min(half, P), pl->ncu, pl->row2)) {
-                const bool pair = (pl->pair >= 0 ? pl->pair : pair_mode()) != 0;
+                const bool pair = pl->pair != 0;
                 const int lo_c = add_list(wl);
                 int64_t tiles_all = 0;
                 const int tp = add_prefix(wl, ofl::kColLog, tiles_all);
@@ -3430,7 +2954,7 @@ void build_schedule(ofl_eden_plan* pl) {
                     }
                     Launch mid{K_COL, m2, ofl::kRowLog + m1, 1, lo_c, tp, 1, tiles_all};
                     mid.stream = s;
-                    mid.nt = use_mid_nt() && m2 == 7;
+                    mid.nt = m2 == 7;  // it streams its intermediate with nt loads and stores
                     mid.nu = enc ? 1 : 0;  // after every row-A sub-wave: the slice norm
                     L.push_back(mid);
                     for (const SubWave& sw : sws) {
@@ -3444,13 +2968,11 @@ void build_schedule(ofl_eden_plan* pl) {
         std::map<int, std::vector<int32_t>> byp;  // column launches grouped by p
         for (int32_t si : wl) byp[pl->slices[si].logp].push_back(si);
         std::vector<Launch> ce, cd;
-        // heights 1..5 (6) -> one k_col_multi
+        // heights 1..kColMultiMax -> one k_col_multi
         std::vector<std::pair<int, const std::vector<int32_t>*>> mg;
-        if (use_colmulti()) {
-            for (auto& kv : byp)
-                if (kv.first - ofl::kRowLog >= 1 && kv.first - ofl::kRowLog <= mmax) mg.push_back({kv.first - ofl::kRowLog, &kv.second});
-            if (mg.size() < 2) mg.clear();
-        }
+        for (auto& kv : byp)
+            if (kv.first - ofl::kRowLog >= 1 && kv.first - ofl::kRowLog <= kColMultiMax) mg.push_back({kv.first - ofl::kRowLog, &kv.second});
+        if (mg.size() < 2) mg.clear();
         if (!mg.empty()) {
             const int gt = (int)ints.size();
             ints.resize(ints.size() + ofl::kColGroup * mg.size());
@@ -3483,24 +3005,16 @@ void build_schedule(ofl_eden_plan* pl) {
         }
         for (auto& kv : byp) {
             const int r = kv.first - ofl::kRowLog;
-            if (!mg.empty() && r >= 1 && r <= mmax) continue;  // in the k_col_multi launch
+            if (!mg.empty() && r >= 1 && r <= kColMultiMax) continue;  // in the k_col_multi launch
             int64_t tiles = 0;
             const int lo_c = add_list(kv.second);
             const int tp = add_prefix(kv.second, ofl::kColLog, tiles);
             const int cnt = (int)kv.second.size();
             std::vector<Launch> seq;
             if (r <= 10) {
-                if ((r == 9 || r == 10) && use_col16()) {  // 2^16-element tiles: 2x longer row segments
-                    int64_t t16 = 0;
-                    const int tp16 = add_prefix(kv.second, 16, t16);
-                    Launch l{K_COL, r, ofl::kRowLog, 1, lo_c, tp16, cnt, t16};
-                    l.tl = 16;
-                    seq.push_back(l);
-                } else {
-                    seq.push_back({K_COL, r, ofl::kRowLog, 1, lo_c, tp, cnt, tiles});
-                    if (r == 10 && use_col6() && use_perm25())  // k_col6<10, true, 15>: interleaved ws
-                        for (int32_t si : kv.second) pl->slices[si].perm = 1;
-                }
+                seq.push_back({K_COL, r, ofl::kRowLog, 1, lo_c, tp, cnt, tiles});
+                if (r == 10)  // k_col6<10, true, 15>: interleaved ws (256-B segments in the middle pass)
+                    for (int32_t si : kv.second) pl->slices[si].perm = 1;
             } else {  // two column levels; the middle launch carries D2
                 const int m1 = r / 2, m2 = r - m1;
                 seq.push_back({K_COL, m1, ofl::kRowLog, 0, lo_c, tp, cnt, tiles});
@@ -3796,12 +3310,11 @@ static int side_pool(int dev, hipStream_t (&out)[3]) {
     for (int i = 0; i < 3; ++i) out[i] = e[i];
     return OFL_OK;
 }
-static int shared_side_streams(int dev, bool two, bool three, hipStream_t& s1, hipStream_t& s2, hipStream_t& s3) {
+static int shared_side_streams(int dev, bool two, hipStream_t& s1, hipStream_t& s2) {
     hipStream_t e[3];
     if (int rc = side_pool(dev, e)) return rc;
     s1 = e[0];
     s2 = two ? e[1] : nullptr;
-    s3 = three ? e[2] : nullptr;
     return OFL_OK;
 }
 
@@ -3822,15 +3335,14 @@ static int ensure_device(ofl_eden_plan_t pl) {
     bool side = false;
     for (const Launch& l : pl->enc) side |= l.stream != 0;
     for (const Launch& l : pl->dec) side |= l.stream != 0;
-    bool side3 = false, side4 = false;
-    for (const Launch& l : pl->enc) { side3 |= l.stream >= 2; side4 |= l.stream == 3; }
-    for (const Launch& l : pl->dec) { side3 |= l.stream >= 2; side4 |= l.stream == 3; }
+    bool small = false;  // the small-slice stream
+    for (const Launch& l : pl->enc) small |= l.stream == 2;
+    for (const Launch& l : pl->dec) small |= l.stream == 2;
     if (side) {
-        if (int rc = shared_side_streams(pl->device, side3, side4, pl->side, pl->side2, pl->side3)) return rc;
+        if (int rc = shared_side_streams(pl->device, small, pl->side, pl->side2)) return rc;
         HIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&pl->ev_join, hipEventDisableTiming));
-        if (side3) HIP_TRY(hipEventCreateWithFlags(&pl->ev_join2, hipEventDisableTiming));
-        if (side4) HIP_TRY(hipEventCreateWithFlags(&pl->ev_join3, hipEventDisableTiming));
+        if (small) HIP_TRY(hipEventCreateWithFlags(&pl->ev_join2, hipEventDisableTiming));
     }
     pl->uploaded = true;
     return OFL_OK;
@@ -3853,7 +3365,6 @@ void ofl_eden_plan_destroy(ofl_eden_plan_t pl) {
     if (pl->d_slices) (void)hipFree(pl->d_slices);
     if (pl->d_ints) (void)hipFree(pl->d_ints);
     if (pl->ev_join2) (void)hipEventDestroy(pl->ev_join2);
-    if (pl->ev_join3) (void)hipEventDestroy(pl->ev_join3);
     if (pl->ev_fork) (void)hipEventDestroy(pl->ev_fork);
     if (pl->ev_join) (void)hipEventDestroy(pl->ev_join);
     delete pl;

@@ -693,9 +693,9 @@ def test_row2_variants_bit_identical():
 
 
 def test_small_launch_split_bit_identical():
-    """Tiny / small slices on the side stream(s) (two of them with
-    OFL_EDEN_SMALL2=1) give the same bytes as one stream: a mixed set through
-    the default two-stream schedule vs the single-stream schedule."""
+    """Tiny / small slices on their side stream give the same bytes as on the
+    caller's stream: a mixed set through the default two-stream schedule vs
+    the single-stream schedule."""
     from openfl_amd.codec import EdenPlan
     numels = [300, 2000, 5000, 9000, 17000, 33000, 70000, 1 << 20, (1 << 21) + 99, 150]
     res = []

@@ -175,7 +175,7 @@ def test_small_set_launch():
         n0 = [l["name"] for l in off.launches(enc)]
         # ResNet-50's large slices fit one wave with a k_col_multi launch, so
         # the small-set groups ride in that launch (k_*_colm_set, on the
-        # caller's stream) unless OFL_EDEN_FUSESET=0 keeps them apart
+        # caller's stream) unless fuse=0 keeps them apart
         fused = f"ofl::k_{d}_colm_set" in n1
         assert n1.count(f"ofl::k_{d}_sset") + n1.count(f"ofl::k_{d}_colm_set") == 1
         assert fused != ("ofl::k_col_multi" in n1)
@@ -327,7 +327,7 @@ def test_split_slice_honours_row2_and_pair():
         assert [l["blocks"] for l in rows] == [2048, 2048]
         assert rows[0]["name"] == f"ofl::k_{d}_rowA" and rows[0]["grid"] == 256
         if enc:  # encode pass C has its two-blocks-per-CU kernel whatever row2 says
-            assert rows[1]["name"].startswith("ofl::k_enc_rowC2<") and rows[1]["grid"] == 512
+            assert rows[1]["name"] == "ofl::k_enc_rowC2" and rows[1]["grid"] == 512
         else:
             assert rows[1]["name"] == "ofl::k_dec_rowC" and rows[1]["grid"] == 256
         assert [l["name"] for l in L if "col" in l["name"]] == ["ofl::k_col<5, false>", "ofl::k_col<6, true>",
@@ -413,14 +413,49 @@ def test_variant_configs_cover_every_row_kernel():
         ("enc", "k_enc_rowC2", False, False), ("enc", "k_enc_rowC2", True, False),
     }
     assert wanted <= reached, sorted(wanted - reached)
-    # Not reachable from the public setters, so in no config:
-    #  * k_enc_rowC (the persistent encode pass C): only the process-wide
-    #    OFL_EDEN_ROWC2=0 selects it, and the environment knobs are read once
-    #    per process;
-    #  * paired k_dec_rowA2 / k_enc_rowC2: these passes apply no D1 signs, and
-    #    only the sign-applying passes have a paired table.
-    unreachable = {("enc", "k_enc_rowC", False, False), ("dec", "k_dec_rowA2", False, True),
-                   ("dec", "k_dec_rowA2", True, True), ("enc", "k_enc_rowC2", False, True),
-                   ("enc", "k_enc_rowC2", True, True)}
+    # In no plan: paired k_dec_rowA2 / k_enc_rowC2 -- these passes apply no D1
+    # signs, and only the sign-applying passes have a paired table.
+    unreachable = {("dec", "k_dec_rowA2", False, True), ("dec", "k_dec_rowA2", True, True),
+                   ("enc", "k_enc_rowC2", False, True), ("enc", "k_enc_rowC2", True, True)}
     assert not (unreachable & reached)
     assert reached == wanted
+
+
+_SCHEDULE_DUMP = """
+import json
+from openfl_amd.codec import EdenPlan
+p = EdenPlan([1 << 26, 1 << 21, 1 << 25, 5000, 300], 8, wave_mib=64)
+d = EdenPlan([1 << 22] * 6, 8)  # 96 MiB of intermediates at the default wave size
+print(json.dumps({"n_waves": p.n_waves, "enc": p.launches(True), "dec": p.launches(False), "default_n_waves": d.n_waves}))
+"""
+
+
+def _schedule_dumps(envs):
+    """The dump of one fresh child process per environment (side by side)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = {k: v for k, v in os.environ.items() if not k.startswith("OFL_EDEN_")}
+    procs = [subprocess.Popen([sys.executable, "-c", _SCHEDULE_DUMP], cwd=root, env={**base, **env},
+                              stdout=subprocess.PIPE, text=True) for env in envs]
+    outs = [p.communicate()[0] for p in procs]
+    assert all(p.returncode == 0 for p in procs)
+    return [json.loads(o) for o in outs]
+
+
+def test_schedule_ignores_the_removed_environment_knobs():
+    """The planner reads OFL_EDEN_WAVE_MIB and OFL_EDEN_STREAMS and nothing
+    else: a process with former A/B knobs set builds the schedule of a process
+    without them (every field launches() reports, both directions).
+    OFL_EDEN_WAVE_MIB still sets the default wave size: six 2^22 slices are one
+    wave at the built-in 128 MiB and three at 32 MiB (the dumped plan sets its
+    wave size itself, and its three large slices are a wave each at either
+    size, so a second plan shows it).  Plan creation is host-only."""
+    removed = {"OFL_EDEN_ROWC2": "0", "OFL_EDEN_COL16": "1", "OFL_EDEN_WAVESORT": "0", "OFL_EDEN_COLM6": "0",
+               "OFL_EDEN_SSET": "0", "OFL_EDEN_PAIR": "0", "OFL_EDEN_BIGSPLIT": "0"}
+    plain, knobs, wave32 = _schedule_dumps([{}, removed, {"OFL_EDEN_WAVE_MIB": "32"}])
+    assert plain["enc"] and plain["dec"]
+    assert knobs == plain
+    assert wave32["default_n_waves"] != plain["default_n_waves"]

@@ -1,7 +1,8 @@
 #!/bin/bash
-# Build libofl_codec.so from the WORKING TREE with extra hipcc flags (tuning
-# constants such as -DOFL_LD_AUX=2) for A/Bs with OFL_CODEC_LIB:
+# Build libofl_codec.so from the WORKING TREE with extra hipcc flags for A/Bs
+# with OFL_CODEC_LIB, e.g. a ladder rung after `git apply tools/ab/ladder.patch`:
 #   bash tools/build_flags_variant.sh OUT.so [extra hipcc flags]
+#   bash tools/build_flags_variant.sh abvar/libofl_lad1.so -DOFL_LADDER=1
 set -euo pipefail
 OUT=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd)
