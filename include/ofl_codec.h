@@ -491,6 +491,50 @@ int ofl_gmedian_delta(int ncollab, const float* const* xs, const double* w0, int
 int ofl_agg_delta_seeds(const void* agg_dev, int agg_is_f64, const float* base, int nranges, const int64_t* starts_dev,
                         const int64_t* dst_dev, int64_t total, const int64_t* draws_dev, uint32_t* seeds_dev,
                         double* sums_dev, void* packed_dev, void* stream);
+/* The FedOpt server optimisers a plan can name in aggregation_type
+ * (adam_adaptive_aggregation.py, yogi_..., adagrad_...; core/
+ * adaptive_aggregation.py:38-113 on utilities/optimizers/numpy/
+ * {adam,yogi,adagrad}_optimizer.py).
+ *
+ * ofl_adaptive_step  One optimiser step over n elements of float32 arenas, bit
+ *                 for bit what the reference computes for float32 parameters
+ *                 and Python-float collaborator weights -- every operation one
+ *                 float32 operation in this order, no contraction:
+ *                   g = +0.0f; for c in order: g = g + w[c] * (base - x[c])
+ *                   ADAM     m = beta1 * m + one_minus_beta1 * g
+ *                            v = beta2 * v + one_minus_beta2 * (g * g)
+ *                            p = p - (lr * (m / bias1)) / (sqrtf(v / bias2) + eps)
+ *                   YOGI     as ADAM, but  s = np.sign(g * g - v)  (NaN for NaN)
+ *                            v = beta2 * v + (one_minus_beta2 * s) * (g * g)
+ *                   ADAGRAD  v = v + g * g
+ *                            p = p - (lr * g) / (sqrtf(v) + eps)
+ *                 The constants are the host's: each Python-float expression
+ *                 (1.0 - beta1, 1.0 - beta1 ** t with t = steps taken + 1, ...)
+ *                 evaluated in double and rounded to float32 once.  xs: host
+ *                 array of 1 <= ncollab <= 128 device pointers (<= 16: unrolled
+ *                 from the kernel arguments, above: a loop over a pointer table
+ *                 in the arguments; more -> OFL_EINVAL); weights: host
+ *                 [ncollab], already rounded to float32; base: device,
+ *                 required.  p, m, v: the device state, updated in place (m is
+ *                 not touched by ADAGRAD and may be NULL there).  Outputs
+ *                 (device, either may be NULL): agg_out = p after the step,
+ *                 delta_out = p after the step - base as a float32 subtract
+ *                 (generate_delta of two float32 arrays).  16-byte vector body
+ *                 when every pointer is 16-byte aligned, a scalar tail; reads
+ *                 4 * ncollab + 16 bytes per element and writes 12 to 20
+ *                 (ADAGRAD: 4 * ncollab + 12 and 8 to 16).  One launch, async. */
+enum { OFL_ADAPTIVE_ADAM = 0, OFL_ADAPTIVE_YOGI = 1, OFL_ADAPTIVE_ADAGRAD = 2 };
+typedef struct {
+    int32_t kind;            /* OFL_ADAPTIVE_* */
+    float lr;
+    float beta1, one_minus_beta1;
+    float beta2, one_minus_beta2;
+    float bias1, bias2;      /* 1 - beta1 ** t, 1 - beta2 ** t */
+    float eps;
+} ofl_adaptive_consts;
+int ofl_adaptive_step(int ncollab, const float* const* xs, const float* weights, const float* base, int64_t n,
+                      float* p, float* m, float* v, const ofl_adaptive_consts* k, float* agg_out, float* delta_out,
+                      void* stream);
 
 /* ---- gzip of rank arrays (csrc/deflate_kernels.hip) -------------------------
  * GZIPTransformer.forward (kc_pipeline.py:128-141, skc_pipeline.py:201-215,

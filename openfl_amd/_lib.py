@@ -36,6 +36,7 @@ EXPORTS = (
     "ofl_wavg_points_workspace_bytes", "ofl_wavg_delta_points", "ofl_apply_delta",
     "ofl_apply_delta_ranges", "ofl_wavg_delta32_ranges", "ofl_sub_f32_f64",
     "ofl_median_delta", "ofl_gmedian_workspace_bytes", "ofl_gmedian_delta", "ofl_agg_delta_seeds",
+    "ofl_adaptive_step",
     "ofl_gzip_last_error", "ofl_gzip_ranks_workspace_bytes", "ofl_gzip_ranks_bound", "ofl_gzip_ranks", "ofl_gzip_ranks_to", "ofl_gzip_label_to", "ofl_side_stream",
     "ofl_gunzip_members", "ofl_gzip_member_index", "ofl_inflate_members", "ofl_inflate_tlz_workspace_bytes",
     "ofl_inflate_tlz", "ofl_inflate_tlz_async", "ofl_inflate_tlz_wait", "ofl_inflate_tlz_launch", "ofl_inflate_tlz_launch_lut", "ofl_inflate_tlz_check", "ofl_gzip_profile", "ofl_gzip_profile_collect",
@@ -187,6 +188,8 @@ def _bind(L):
     L.ofl_gmedian_delta.restype = i32
     L.ofl_agg_delta_seeds.argtypes = [vp, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp]
     L.ofl_agg_delta_seeds.restype = i32
+    L.ofl_adaptive_step.argtypes = [i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.ofl_adaptive_step.restype = i32
     L.ofl_gzip_last_error.restype = ctypes.c_char_p
     L.ofl_gzip_ranks_workspace_bytes.argtypes = [i64]
     L.ofl_gzip_ranks_workspace_bytes.restype = sz

@@ -23,7 +23,15 @@ payloads, metadata, np.random draws and new model are identical to calling
 the reference's functions tensor by tensor with an openfl_amd EdenPipeline
 (tests/test_gpu_aggregation.py).  No CPU fallback: without the library or a
 GPU every call raises CodecError.
+
+Beside the weighted average: Median and GeometricMedian, and the FedOpt
+server optimisers AdamAdaptiveAggregation, YogiAdaptiveAggregation and
+AdagradAdaptiveAggregation (core/adaptive_aggregation.py on
+utilities/optimizers/numpy/*_optimizer.py), whose parameters and moments stay
+on the device between rounds (ofl_adaptive_step).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -277,6 +285,210 @@ class GeometricMedian:
         return self.call(local_tensors, *args)
 
 
+# ---- FedOpt server optimisers (core/adaptive_aggregation.py:38-113 on
+# utilities/optimizers/numpy/{adam,yogi,adagrad}_optimizer.py) ------------------
+ADAPTIVE_AGGREGATIONS = ("adam", "yogi", "adagrad")   # RoundEnd(aggregation=...) beside AGGREGATIONS
+_ADAPTIVE_KIND = {"adam": 0, "yogi": 1, "adagrad": 2}  # OFL_ADAPTIVE_*
+_ADAPTIVE_MAX_C = 128                                  # ofl_adaptive_step: <= 16 unrolled, <= 128 from a table
+
+
+class _AdaptiveConsts(ctypes.Structure):  # ofl_adaptive_consts
+    _fields_ = [("kind", ctypes.c_int32), ("lr", ctypes.c_float), ("beta1", ctypes.c_float),
+                ("one_minus_beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("one_minus_beta2", ctypes.c_float),
+                ("bias1", ctypes.c_float), ("bias2", ctypes.c_float), ("eps", ctypes.c_float)]
+
+
+class AdaptiveHyper:
+    """The hyper-parameters of one optimiser kind ("adam", "yogi", "adagrad"),
+    checked as the reference checks them (adam_optimizer.py:75-87,
+    adagrad_optimizer.py:68-76; the same ValueErrors) and with its defaults.
+    They are Python floats, as a plan gives them."""
+
+    def __init__(self, kind, learning_rate=0.01, betas=None, initial_accumulator_value=None, epsilon=None):
+        if kind not in _ADAPTIVE_KIND:
+            raise _lib.CodecError(f"optimiser kind must be one of {ADAPTIVE_AGGREGATIONS}, not {kind!r}")
+        adagrad = kind == "adagrad"
+        if adagrad and betas is not None:
+            raise TypeError("adagrad has no betas")
+        betas = (0.9, 0.999) if betas is None else betas
+        if initial_accumulator_value is None:
+            initial_accumulator_value = 0.1 if adagrad else 0.0
+        if epsilon is None:
+            epsilon = 1e-10 if adagrad else 1e-8
+        if learning_rate < 0:
+            raise ValueError(f"Invalid learning rate: {learning_rate}. Learning rate must be >= 0.")
+        if not adagrad:
+            if not 0.0 <= betas[0] < 1:
+                raise ValueError(f"Invalid betas[0] value: {betas[0]}. betas[0] must be in [0, 1).")
+            if not 0.0 <= betas[1] < 1:
+                raise ValueError(f"Invalid betas[1] value: {betas[1]}. betas[1] must be in [0, 1).")
+        if initial_accumulator_value < 0:
+            raise ValueError(f"Invalid initial_accumulator_value value: {initial_accumulator_value}. "
+                             "Initial accumulator value must be >= 0.")
+        if epsilon <= 0:
+            raise ValueError(f"Invalid epsilon value: {epsilon}. Epsilon avalue must be > 0.")
+        self.kind = kind
+        self.learning_rate = float(learning_rate)
+        self.beta_1, self.beta_2 = float(betas[0]), float(betas[1])
+        self.initial_accumulator_value = float(initial_accumulator_value)
+        self.epsilon = float(epsilon)
+
+    def consts(self, steps_taken):
+        """ofl_adaptive_consts for the step after `steps_taken`: every Python-float
+        expression of the reference evaluated in double, then rounded to
+        float32 once (what NumPy does with a Python float beside a float32 array)."""
+        f = lambda x: float(np.float32(x))  # noqa: E731
+        b1, b2, t = self.beta_1, self.beta_2, int(steps_taken) + 1
+        if self.kind == "adagrad":
+            return _AdaptiveConsts(2, f(self.learning_rate), 0, 0, 0, 0, 1, 1, f(self.epsilon))
+        return _AdaptiveConsts(_ADAPTIVE_KIND[self.kind], f(self.learning_rate), f(b1), f(1.0 - b1), f(b2), f(1.0 - b2),
+                               f(1.0 - b1 ** t), f(1.0 - b2 ** t), f(self.epsilon))
+
+
+def _f32_weights(name, weights):
+    """The collaborator weights as the float32 values the reference's gradient
+    multiplies by: a Python int / float beside a float32 array is rounded to
+    float32 (np.float32: as it is).  Any other NumPy scalar would promote the
+    gradient to float64 under NumPy >= 2, which is not implemented."""
+    out = np.empty(len(weights), np.float32)
+    for c, w in enumerate(weights):
+        if isinstance(w, np.generic) and not isinstance(w, np.float32):
+            raise _lib.CodecError(
+                f"{name}: weight {c} is a {type(w).__name__}; with it NumPy >= 2 computes the reference's gradient "
+                "in float64, which is not implemented -- pass Python floats (data_size / weight_total) or np.float32")
+        if not isinstance(w, (int, float, np.float32)):
+            raise _lib.CodecError(f"{name}: weight {c} must be a Python int or float or a np.float32")
+        out[c] = np.float32(w)
+    return out
+
+
+def adaptive_step(hyper, steps_taken, xs, weights32, base, n, p, m, v, agg_out=None, delta_out=None, device=None):
+    """One ofl_adaptive_step launch on the current stream: n elements of the
+    float32 device tensors xs (collaborators, at most 128), base and the state
+    p, m, v (updated in place; m may be None for adagrad), the step after
+    `steps_taken`; agg_out = new p and delta_out = new p - base if given."""
+    _check_collaborators(hyper.kind, len(xs), _ADAPTIVE_MAX_C)
+    if len(xs) < 1 or len(weights32) != len(xs):
+        raise _lib.CodecError(f"{hyper.kind}: one float32 weight per collaborator tensor, at least one")
+    ptrs = np.asarray([x.data_ptr() for x in xs], np.uint64)
+    w32 = np.ascontiguousarray(weights32, np.float32)
+    k = hyper.consts(steps_taken)
+    _lib.check_agg(_lib.lib().ofl_adaptive_step(
+        len(xs), ptrs.ctypes.data, w32.ctypes.data, base.data_ptr(), int(n), p.data_ptr(),
+        m.data_ptr() if m is not None else None, v.data_ptr(), ctypes.addressof(k),
+        agg_out.data_ptr() if agg_out is not None else None, delta_out.data_ptr() if delta_out is not None else None,
+        _stream(device)))
+
+
+class _AdaptiveAggregation:
+    """AdaptiveAggregation (core/adaptive_aggregation.py:16-113) with the
+    optimiser's state on the device.  params: dict name -> float32 array, the
+    parameters the optimiser owns (copied to the device; unlike the reference
+    the caller's arrays are not updated in place).  model_interface is not
+    offered: it needs the framework adapters to read a model's tensors.
+    call() gives the reference's bits for float32 tensors and Python-float (or
+    np.float32) weights; other NumPy weight types are refused (see
+    _f32_weights)."""
+    kind = None
+
+    def __init__(self, *, params, agg_func=None, device=None, **hyper):
+        self.hyper = AdaptiveHyper(self.kind, **hyper)
+        if params is None:
+            raise ValueError("Should provide params (model_interface is not supported)")
+        self.default_agg_func = agg_func if agg_func is not None else WeightedAverage(device)
+        self.device = resolve_device(device)
+        self._shape, self._p, self._m, self._v = {}, {}, {}, {}
+        self.current_step = {}
+        for name, arr in params.items():
+            a = np.asarray(arr)
+            if a.dtype != np.float32:
+                raise _lib.CodecError(f"{self.kind}: parameter {name!r} must be float32, not {a.dtype}")
+            self._shape[name] = a.shape
+            flat = np.ascontiguousarray(a).reshape(-1)
+            with torch.cuda.device(self.device):
+                self._p[name] = torch.from_numpy(flat.copy()).to(self.device)
+                acc = self.hyper.initial_accumulator_value
+                self._m[name] = torch.full_like(self._p[name], acc) if self.kind != "adagrad" else None
+                self._v[name] = torch.full_like(self._p[name], acc)
+            self.current_step[name] = 0
+
+    @property
+    def params(self):
+        return self._shape.keys()
+
+    def state(self, name):
+        """Host copies of the device state of one parameter: p, m (None for
+        adagrad), v in the parameter's shape, and the steps taken."""
+        sh = self._shape[name]
+        get = lambda t: None if t is None else t.cpu().numpy().reshape(sh)  # noqa: E731
+        return {"params": get(self._p[name]), "first_moment": get(self._m[name]),
+                "second_moment": get(self._v[name]), "step": self.current_step[name]}
+
+    def set_state(self, name, first_moment=None, second_moment=None, step=None):
+        """Overwrite parts of one parameter's state (a restored checkpoint):
+        float32 arrays of the parameter's shape, the steps already taken."""
+        for store, arr in ((self._m, first_moment), (self._v, second_moment)):
+            if arr is None:
+                continue
+            a = np.asarray(arr)
+            if a.dtype != np.float32 or a.shape != self._shape[name] or store[name] is None:
+                raise _lib.CodecError(f"{self.kind}: state of {name!r} must be float32 of shape {self._shape[name]}")
+            store[name] = torch.from_numpy(np.ascontiguousarray(a).reshape(-1).copy()).to(self.device)
+        if step is not None:
+            self.current_step[name] = int(step)
+
+    def call(self, local_tensors, db_iterator, tensor_name, fl_round, tags):
+        if tensor_name not in self._shape:
+            return self.default_agg_func(local_tensors, db_iterator, tensor_name, fl_round, tags)
+        base = None
+        search_tag = "aggregated" if fl_round != 0 else "model"
+        for record in db_iterator:
+            if (record["round"] == fl_round and record["tensor_name"] == tensor_name
+                    and search_tag in record["tags"] and "delta" not in record["tags"]):
+                base = record["nparray"]
+        if base is None:
+            raise KeyError(f"There is no current global model in TensorDB for tensor name: {tensor_name}")
+        arrs, shape, n = _f32_stack(self.kind, [x.tensor for x in local_tensors] + [base])
+        if shape != self._shape[tensor_name]:
+            raise _lib.CodecError(f"{self.kind}: {tensor_name!r} has shape {self._shape[tensor_name]}, not {shape}")
+        w32 = _f32_weights(self.kind, [x.weight for x in local_tensors])
+        if len(arrs) < 2:
+            raise _lib.CodecError(f"{self.kind}: no tensors")
+        _check_collaborators(self.kind, len(arrs) - 1, _ADAPTIVE_MAX_C)
+        dev = self.device
+        p = self._p[tensor_name]
+        with torch.cuda.device(dev):
+            if n:
+                ts = [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev) for a in arrs]
+                adaptive_step(self.hyper, self.current_step[tensor_name], ts[:-1], w32, ts[-1], n, p,
+                              self._m[tensor_name], self._v[tensor_name], device=dev)
+            self.current_step[tensor_name] += 1
+            return p.cpu().numpy().reshape(shape)
+
+    def __call__(self, local_tensors, *args):
+        return self.call(local_tensors, *args)
+
+
+class AdamAdaptiveAggregation(_AdaptiveAggregation):
+    """adam_adaptive_aggregation.py:18-57 (NumPyAdam): AdamAdaptiveAggregation(*,
+    params, agg_func=WeightedAverage(), learning_rate=0.01, betas=(0.9, 0.999),
+    initial_accumulator_value=0.0, epsilon=1e-8, device=None)."""
+    kind = "adam"
+
+
+class YogiAdaptiveAggregation(_AdaptiveAggregation):
+    """yogi_adaptive_aggregation.py (NumPyYogi): the arguments and defaults of
+    AdamAdaptiveAggregation."""
+    kind = "yogi"
+
+
+class AdagradAdaptiveAggregation(_AdaptiveAggregation):
+    """adagrad_adaptive_aggregation.py (NumPyAdagrad): AdagradAdaptiveAggregation(*,
+    params, agg_func=WeightedAverage(), learning_rate=0.01,
+    initial_accumulator_value=0.1, epsilon=1e-10, device=None); no betas."""
+    kind = "adagrad"
+
+
 class RoundEnd:
     """Aggregator._prepare_trained for a whole model update (aggregator.py:780-865).
 
@@ -295,12 +507,34 @@ class RoundEnd:
     robust aggregators write the delta arena with their own kernels, take the
     seeds from it (ofl_agg_delta_seeds) and are never fused; everything after
     the seeds is the same code.
+    aggregation "adam", "yogi" or "adagrad" (ADAPTIVE_AGGREGATIONS): the FedOpt
+    server optimisers (AdaptiveAggregation over NumPyAdam / NumPyYogi /
+    NumPyAdagrad), at most 128 collaborators, agg_out float32.  optimizer: a
+    dict of the optimiser's hyper-parameters (learning_rate, betas,
+    initial_accumulator_value, epsilon; the reference's defaults and checks).
+    Every tensor of the layout is optimised -- what a plan's model_interface
+    gives, whose whole tensor dict is the optimiser's params; leaving single
+    tensors to another aggregation function is not offered here (the plugins
+    do it).  The state (parameters, first and second moment, step count)
+    lives in arenas of this layout: init_optimizer(params_arena) before the
+    first run(), optimizer_state() to read it.  run() needs base_arena (the
+    gradient is formed against it), takes one ofl_adaptive_step over the
+    arena, then the seeds from the float32 delta as the median does; never
+    fused.  The aggregate is the reference's bit for bit for Python-float (or
+    np.float32) weights; other NumPy weight types are refused.
     """
 
-    def __init__(self, pipeline, shapes, device=None, fused=True, aggregation="weighted_average"):
-        if aggregation not in AGGREGATIONS:
-            raise _lib.CodecError(f"aggregation must be one of {AGGREGATIONS}, not {aggregation!r}")
+    def __init__(self, pipeline, shapes, device=None, fused=True, aggregation="weighted_average", optimizer=None):
+        if aggregation not in AGGREGATIONS + ADAPTIVE_AGGREGATIONS:
+            raise _lib.CodecError(
+                f"aggregation must be one of {AGGREGATIONS + ADAPTIVE_AGGREGATIONS}, not {aggregation!r}")
         self.aggregation = aggregation
+        if aggregation in ADAPTIVE_AGGREGATIONS:
+            self._hyper = AdaptiveHyper(aggregation, **(optimizer or {}))
+        elif optimizer is not None:
+            raise _lib.CodecError(f"optimizer= belongs to the aggregations {ADAPTIVE_AGGREGATIONS}")
+        self._opt = None   # (p, m, v) arenas after init_optimizer
+        self._opt_step = 0
         tr = pipeline.transformers[0]
         self.transformer = tr
         self.device = resolve_device(device) if device is not None else tr.eden.device
@@ -388,6 +622,30 @@ class RoundEnd:
     def view(self, arena, i):
         return arena[self.offsets[i]:self.offsets[i] + self.numels[i]].view(self.shapes[i])
 
+    # -- the optimiser's state (aggregation "adam" / "yogi" / "adagrad") --
+    def init_optimizer(self, params_arena):
+        """Start the optimiser from a copy of params_arena (this layout): first
+        and second moment filled with initial_accumulator_value, no steps taken."""
+        if self.aggregation not in ADAPTIVE_AGGREGATIONS:
+            raise _lib.CodecError(f"aggregation {self.aggregation!r} has no optimizer")
+        x = params_arena
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= self.arena_numel):
+            raise _lib.CodecError("arenas must be contiguous float32 device tensors of arena_numel elements")
+        with torch.cuda.device(self.device):
+            p = x[:self.arena_numel].to(self.device, copy=True)
+            acc = self._hyper.initial_accumulator_value
+            m = torch.full_like(p, acc) if self.aggregation != "adagrad" else None
+            self._opt = (p, m, torch.full_like(p, acc))
+        self._opt_step = 0
+
+    def optimizer_state(self):
+        """The live state arenas (not copies) and the steps taken:
+        {"params", "first_moment" (None for adagrad), "second_moment", "step"}."""
+        if self._opt is None:
+            raise _lib.CodecError("init_optimizer(params_arena) has not been called")
+        p, m, v = self._opt
+        return {"params": p, "first_moment": m, "second_moment": v, "step": self._opt_step}
+
     def _wsum(self, w64):
         sums = {weight_sum(w64, d) for d in {len(s) for s in self.shapes}}
         if len(sums) != 1:
@@ -405,7 +663,9 @@ class RoundEnd:
         the float64 average into agg_out (arena_numel elements).  With
         aggregation "median" the weights are ignored (may be None) and agg_out
         is float32; with "geometric_median" agg_out is float64 and is written
-        inside the tensors only.
+        inside the tensors only.  With "adam", "yogi" or "adagrad" the weights
+        are Python floats (or np.float32), base_arena is required, agg_out is
+        float32 (the parameters after the step) and the step count rises by one.
         -> (new model arena, [(payload bytes, [metadata])] per tensor or None,
         seeds: a list with payloads, else the device int32 tensor -- without
         payloads nothing synchronises with the host)."""
@@ -414,7 +674,8 @@ class RoundEnd:
         for x in xs + ([base_arena] if base_arena is not None else []):
             if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= self.arena_numel):
                 raise _lib.CodecError("arenas must be contiguous float32 device tensors of arena_numel elements")
-        agg_dtype = torch.float32 if self.aggregation == "median" else torch.float64
+        f32_agg = self.aggregation == "median" or self.aggregation in ADAPTIVE_AGGREGATIONS
+        agg_dtype = torch.float32 if f32_agg else torch.float64
         if agg_out is not None and not (agg_out.dtype == agg_dtype and agg_out.numel() >= self.arena_numel):
             raise _lib.CodecError(f"agg_out must be {str(agg_dtype)[6:]} with arena_numel elements")
         if self.aggregation != "weighted_average":
@@ -475,14 +736,32 @@ class RoundEnd:
         return self._dev_args.data_ptr()
 
     def _run_robust(self, xs, weights, base_arena, agg_out, payloads, out):
-        """run() for "median" and "geometric_median": the delta arena from
-        their kernels, the seeds from that delta, then the shared tail."""
+        """run() for every aggregation but the weighted average: the delta
+        arena from their kernels, the seeds from that delta, then the shared tail."""
         dev = self.device
         L = _lib.lib()
         T = len(self.numels)
+        if self.aggregation in ADAPTIVE_AGGREGATIONS:
+            if self._opt is None:
+                raise _lib.CodecError(f"{self.aggregation}: call init_optimizer(params_arena) before run()")
+            if base_arena is None:
+                raise _lib.CodecError(f"{self.aggregation}: base_arena is required, the gradient is formed against it")
+            _check_collaborators(self.aggregation, len(xs), _ADAPTIVE_MAX_C)
+            if weights is None or len(weights) != len(xs) or not xs:
+                raise _lib.CodecError("one weight per collaborator tensor")
+            weights = _f32_weights(self.aggregation, list(weights))
         with torch.cuda.device(dev):
             delta = torch.empty(self.arena_numel, dtype=torch.float32, device=dev)
-            if self.aggregation == "median":
+            if self.aggregation in ADAPTIVE_AGGREGATIONS:
+                # one elementwise step over the whole arena (in the alignment gaps
+                # everything is zero: a zero gradient); the float32 delta it
+                # writes is generate_delta of two float32 arrays
+                p, m, v = self._opt
+                adaptive_step(self._hyper, self._opt_step, xs, weights, base_arena, self.arena_numel, p, m, v,
+                              agg_out=agg_out, delta_out=delta, device=dev)
+                self._opt_step += 1
+                src, is_f64, seed_base = delta, 0, None
+            elif self.aggregation == "median":
                 # elementwise over the whole arena; the float32 delta it writes
                 # is the array the seed formula sums
                 _median_launch(xs, base_arena, self.arena_numel, med=agg_out, delta=delta, device=dev)

@@ -1114,3 +1114,222 @@ int ofl_agg_delta_seeds(const void* agg_dev, int agg_is_f64, const float* base, 
 }
 
 }  // extern "C"
+
+// ---- FedOpt server optimisers: Adam, Yogi and Adagrad --------------------------
+// (reference: interface/aggregation_functions/core/adaptive_aggregation.py:38-113,
+//  utilities/optimizers/numpy/{adam,yogi,adagrad}_optimizer.py)
+//
+// With float32 parameters and Python-float collaborator weights every operation
+// of the reference is one float32 NumPy operation (a Python float is a weak
+// scalar: it is rounded to float32 once and the array's dtype holds), and none
+// of them is a reduction whose order could differ.  The kernel performs the
+// same float32 operations in the same order, contraction off, with the
+// constants already rounded by the host:
+//   g = +0.0f;  for c in order:  g = g + w_c * (base - x_c)        (sum() from 0)
+//   Adam     m = b1 * m + (1 - b1) * g
+//            v = b2 * v + (1 - b2) * (g * g)
+//            p = p - (lr * (m / (1 - b1^t))) / (sqrtf(v / (1 - b2^t)) + eps)
+//   Yogi     as Adam, v = b2 * v + ((1 - b2) * sign(g * g - v)) * (g * g)
+//   Adagrad  v = v + g * g;  p = p - (lr * g) / (sqrtf(v) + eps)
+// `/` and sqrtf are the correctly rounded float32 operations and float32
+// denormals are kept, as in NumPy.  Per element the kernel reads 4 C + 16 bytes
+// (collaborators, base, p, m, v; Adagrad: 4 C + 12) and writes 12 to 20 (p, m, v,
+// and the optional aggregate and delta; Adagrad: 8 to 16); the state of an element
+// is read and written by one thread.
+
+namespace agg {
+
+constexpr int kAdaMaxC = 128;  // the pointer table's length
+
+struct AdaIO {
+    const float* base;
+    float* p;
+    float* m;      // unused by Adagrad
+    float* v;
+    float* agg;    // nullable: p after the step
+    float* delta;  // nullable: p after the step - base, a float32 subtract
+    int64_t n;
+};
+struct AdaArgs {  // <= 16 collaborators, unrolled
+    const float* x[kMaxC];
+    float w[kMaxC];
+    AdaIO io;
+    ofl_adaptive_consts k;
+};
+struct AdaArgsN {  // 17..128 collaborators, a runtime loop over the table
+    const float* x[kAdaMaxC];
+    float w[kAdaMaxC];
+    int nc;
+    AdaIO io;
+    ofl_adaptive_consts k;
+};
+
+// np.sign: -1, 0, +1, and the NaN itself for a NaN
+__device__ __forceinline__ float np_signf(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : (d == 0.f ? 0.f : d)); }
+
+__device__ __forceinline__ void ada_update(const ofl_adaptive_consts& k, float g, float& p, float& m, float& v) {
+#pragma clang fp contract(off)
+    const float gg = g * g;
+    if (k.kind == OFL_ADAPTIVE_ADAGRAD) {
+        v = v + gg;
+        const float num = k.lr * g;
+        const float den = sqrtf(v) + k.eps;
+        p = p - num / den;
+        return;
+    }
+    {
+        const float a = k.beta1 * m;
+        const float b = k.one_minus_beta1 * g;
+        m = a + b;
+    }
+    if (k.kind == OFL_ADAPTIVE_YOGI) {
+        const float s = np_signf(gg - v);
+        const float a = k.beta2 * v;
+        const float c = k.one_minus_beta2 * s;
+        const float b = c * gg;
+        v = a + b;
+    } else {
+        const float a = k.beta2 * v;
+        const float b = k.one_minus_beta2 * gg;
+        v = a + b;
+    }
+    const float mh = m / k.bias1;
+    const float vh = v / k.bias2;
+    const float num = k.lr * mh;
+    const float den = sqrtf(vh) + k.eps;
+    p = p - num / den;
+}
+
+template <int C, class A>
+__device__ __forceinline__ void ada_elem(const A& a, int64_t i) {
+#pragma clang fp contract(off)
+    const bool moment = a.k.kind != OFL_ADAPTIVE_ADAGRAD;
+    const float b = a.io.base[i];
+    float g = 0.0f;
+    if constexpr (C > 0) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float d = b - a.x[c][i];
+            g = g + a.w[c] * d;
+        }
+    } else {
+        for (int c = 0; c < a.nc; ++c) {
+            const float d = b - a.x[c][i];
+            g = g + a.w[c] * d;
+        }
+    }
+    float p = a.io.p[i], m = moment ? a.io.m[i] : 0.f, v = a.io.v[i];
+    ada_update(a.k, g, p, m, v);
+    a.io.p[i] = p;
+    if (moment) a.io.m[i] = m;
+    a.io.v[i] = v;
+    if (a.io.agg) a.io.agg[i] = p;
+    if (a.io.delta) a.io.delta[i] = p - b;
+}
+
+// 4 consecutive elements per thread, 16-B loads and stores of every arena
+template <int C, class A>
+__device__ __forceinline__ void ada_quad(const A& a, int64_t i) {
+#pragma clang fp contract(off)
+    const bool moment = a.k.kind != OFL_ADAPTIVE_ADAGRAD;
+    const float4 b = *reinterpret_cast<const float4*>(a.io.base + i);
+    float g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, g3 = 0.0f;
+    auto term = [&](const float4 x, const float w) {
+        const float d0 = b.x - x.x, d1 = b.y - x.y, d2 = b.z - x.z, d3 = b.w - x.w;
+        const float t0 = w * d0, t1 = w * d1, t2 = w * d2, t3 = w * d3;
+        g0 = g0 + t0; g1 = g1 + t1; g2 = g2 + t2; g3 = g3 + t3;
+    };
+    if constexpr (C > 0) {
+        float4 q[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) q[c] = *reinterpret_cast<const float4*>(a.x[c] + i);
+#pragma unroll
+        for (int c = 0; c < C; ++c) term(q[c], a.w[c]);
+    } else {
+        for (int c = 0; c < a.nc; ++c) term(*reinterpret_cast<const float4*>(a.x[c] + i), a.w[c]);
+    }
+    float4 p = *reinterpret_cast<const float4*>(a.io.p + i);
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (moment) m = *reinterpret_cast<const float4*>(a.io.m + i);
+    float4 v = *reinterpret_cast<const float4*>(a.io.v + i);
+    ada_update(a.k, g0, p.x, m.x, v.x);
+    ada_update(a.k, g1, p.y, m.y, v.y);
+    ada_update(a.k, g2, p.z, m.z, v.z);
+    ada_update(a.k, g3, p.w, m.w, v.w);
+    *reinterpret_cast<float4*>(a.io.p + i) = p;
+    if (moment) *reinterpret_cast<float4*>(a.io.m + i) = m;
+    *reinterpret_cast<float4*>(a.io.v + i) = v;
+    if (a.io.agg) *reinterpret_cast<float4*>(a.io.agg + i) = p;
+    if (a.io.delta) *reinterpret_cast<float4*>(a.io.delta + i) = make_float4(p.x - b.x, p.y - b.y, p.z - b.z, p.w - b.w);
+}
+
+// C > 0: that many collaborators unrolled from AdaArgs; C == 0: a.nc of AdaArgsN
+template <int C, class A>
+__global__ __launch_bounds__(kNT) void k_adaptive(A a, int vec) {
+    const int64_t stride = (int64_t)gridDim.x * kNT;
+    const int64_t t0 = (int64_t)blockIdx.x * kNT + threadIdx.x;
+    int64_t tail = 0;
+    if (vec) {
+        const int64_t n4 = a.io.n >> 2;
+        for (int64_t q = t0; q < n4; q += stride) ada_quad<C>(a, 4 * q);
+        tail = 4 * n4;
+    }
+    for (int64_t i = tail + t0; i < a.io.n; i += stride) ada_elem<C>(a, i);
+}
+
+}  // namespace agg
+
+namespace {
+template <int C>
+void launch_adaptive(const agg::AdaArgs& a, int vec, hipStream_t st) {
+    hipLaunchKernelGGL((agg::k_adaptive<C, agg::AdaArgs>), dim3(grid_for(a.io.n, 4)), dim3(agg::kNT), 0, st, a, vec);
+}
+}  // namespace
+
+extern "C" {
+
+int ofl_adaptive_step(int ncollab, const float* const* xs, const float* weights, const float* base, int64_t n,
+                      float* p, float* m, float* v, const ofl_adaptive_consts* k, float* agg_out, float* delta_out,
+                      void* stream) {
+    if (ncollab < 1 || !xs || !weights) return afail(OFL_EINVAL, "adaptive step: need at least one collaborator");
+    if (ncollab > agg::kAdaMaxC) return afail(OFL_EINVAL, "adaptive step: at most 128 collaborators");
+    if (n < 0) return afail(OFL_EINVAL, "adaptive step: negative size");
+    if (!k || k->kind < OFL_ADAPTIVE_ADAM || k->kind > OFL_ADAPTIVE_ADAGRAD)
+        return afail(OFL_EINVAL, "adaptive step: kind must be OFL_ADAPTIVE_ADAM, _YOGI or _ADAGRAD");
+    for (int c = 0; c < ncollab; ++c)
+        if (!xs[c]) return afail(OFL_EINVAL, "adaptive step: null collaborator tensor");
+    if (n == 0) return OFL_OK;
+    if (!base || !p || !v || (k->kind != OFL_ADAPTIVE_ADAGRAD && !m))
+        return afail(OFL_EINVAL, "adaptive step: base and the state arenas are required");
+    agg::AdaIO io{base, p, k->kind != OFL_ADAPTIVE_ADAGRAD ? m : nullptr, v, agg_out, delta_out, n};
+    uintptr_t al = reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(io.m) |
+                   reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(agg_out) |
+                   reinterpret_cast<uintptr_t>(delta_out);
+    for (int c = 0; c < ncollab; ++c) al |= reinterpret_cast<uintptr_t>(xs[c]);
+    const int vec = (al & 15u) ? 0 : 1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (ncollab <= agg::kMaxC) {
+        agg::AdaArgs a{};
+        for (int c = 0; c < ncollab; ++c) {
+            a.x[c] = xs[c];
+            a.w[c] = weights[c];
+        }
+        a.io = io;
+        a.k = *k;
+        OFL_FOR_C16(launch_adaptive, ncollab, a, vec, st)
+    } else {
+        agg::AdaArgsN a{};
+        for (int c = 0; c < ncollab; ++c) {
+            a.x[c] = xs[c];
+            a.w[c] = weights[c];
+        }
+        a.nc = ncollab;
+        a.io = io;
+        a.k = *k;
+        hipLaunchKernelGGL((agg::k_adaptive<0, agg::AdaArgsN>), dim3(grid_for(n, 4)), dim3(agg::kNT), 0, st, a, vec);
+    }
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+}  // extern "C"

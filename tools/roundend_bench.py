@@ -87,6 +87,58 @@ def robust(args, pipe, shapes, dev, collabs, w, base, out, nbytes, timed):
     print(json.dumps(line), flush=True)
 
 
+def adaptive(args, pipe, shapes, dev, collabs, w, base, out, nbytes, timed):
+    """--aggregation adam | yogi | adagrad: one JSON line with the round end's
+    step time, ofl_adaptive_step alone (with the float32 delta, without agg_out:
+    4 C + 16 bytes read and 16 written per element, adagrad 4 C + 12 and 12) and,
+    on the same arenas, k_wavg_delta and k_median with their own bytes
+    (4 C + 4 read, 4 written) and the unfused weighted-average round end."""
+    import torch
+    from openfl_amd import aggregation as A
+    C = len(collabs)
+    w = [float(v) for v in w]   # Python floats, as the aggregator passes them
+    re = A.RoundEnd(pipe, shapes, dev, aggregation=args.aggregation)
+    re.init_optimizer(base)
+    re_u = A.RoundEnd(pipe, shapes, dev, fused=False)
+    t_r, t_u = [], []
+    for _ in range(3):
+        t_r.append(timed(lambda: re.run(collabs, w, base, payloads=False, out=out), args.steps, args.warmup))
+        t_u.append(timed(lambda: re_u.run(collabs, w, base, payloads=False, out=out), args.steps, args.warmup))
+    t_pay = timed(lambda: re.run(collabs, w, base, payloads=True, out=out), max(1, args.steps // 2), 1)
+    n = re.arena_numel
+    delta = torch.empty(n, dtype=torch.float32, device=dev)
+    st = re.optimizer_state()
+    w32 = np.asarray(w, np.float32)
+    hyper = A.AdaptiveHyper(args.aggregation)
+    t_k = timed(lambda: A.adaptive_step(hyper, 0, collabs, w32, base, n, st["params"], st["first_moment"],
+                                        st["second_moment"], delta_out=delta, device=dev), args.steps, args.warmup)
+    state = 2 if args.aggregation == "adagrad" else 3
+    moved = n * (4 * C + 4 + 8 * state + 4)
+
+    def rate(t, b):
+        return {"ms": round(1e3 * t, 4), "bytes_moved": b, "GBps": round(b / t / 1e9, 1),
+                "frac_of_peak_hbm": round(b / t / 1e9 / PEAK_HBM_GBPS, 4)}
+    kernel = dict({"kernel": "k_adaptive (one optimiser step + float32 delta)"}, **rate(t_k, moved))
+    w64 = A._f64_weights(w, C)
+    wsum = A.weight_sum(w64, 1)
+    small = n * (4 * C + 4 + 4)
+    t_w = timed(lambda: A._wavg_launch(collabs, w64, wsum, base, n, delta32=delta, device=dev), args.steps, args.warmup)
+    t_m = timed(lambda: A._median_launch(collabs, base, n, delta=delta, device=dev), args.steps, args.warmup)
+    kernel["k_wavg_delta"] = rate(t_w, small)
+    kernel["k_median"] = rate(t_m, small)
+    line = {"metric": f"GiB/s aggregator round end ({args.aggregation} step + delta + Eden encode/decode + apply), "
+                      "device-resident",
+            "value": round(nbytes / min(t_r) / 2 ** 30, 3), "unit": "GiB/s", "n_gpus": 1, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * min(t_r), 3), "higher_is_better": True,
+            "dtype": "f32", "data": "synthetic N(0, 0.01^2) updates and base, resident in HBM",
+            "config": {"workload": args.workload, "tensors": len(shapes), "bytes": nbytes, "collaborators": C,
+                       "n_bits": 8, "seed_mode": args.seed_mode, "aggregation": args.aggregation},
+            "also": {"with_payload_d2h": {"ms_per_step": round(1e3 * t_pay, 3)},
+                     "unfused_weighted_average_same_interleave": {"ms_per_step": round(1e3 * min(t_u), 3)},
+                     "aggregation_alone": kernel}}
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="resnet50_fp32")
@@ -95,9 +147,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seed-mode", default="fast")
     ap.add_argument("--host-steps", type=int, default=1, help="steps of the per-tensor host call pattern (0: skip)")
-    ap.add_argument("--aggregation", default="weighted_average", choices=["weighted_average", "median", "geometric_median"],
-                    help="median / geometric_median: the round end with that aggregator (never fused), its "
-                         "aggregation kernels alone, and the unfused weighted-average round end beside it")
+    ap.add_argument("--aggregation", default="weighted_average", choices=["weighted_average", "median", "geometric_median", "adam", "yogi", "adagrad"],
+                    help="median / geometric_median / adam / yogi / adagrad: the round end with that aggregator "
+                         "(never fused), its aggregation kernels alone, and the unfused weighted-average round "
+                         "end beside it")
     args = ap.parse_args()
 
     import torch
@@ -130,6 +183,8 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / steps
 
+    if args.aggregation in ("adam", "yogi", "adagrad"):
+        return adaptive(args, pipe, shapes, dev, collabs, w, base, out, nbytes, timed)
     if args.aggregation != "weighted_average":
         return robust(args, pipe, shapes, dev, collabs, w, base, out, nbytes, timed)
 
