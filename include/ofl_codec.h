@@ -293,7 +293,8 @@ int ofl_kmeans1d_fit(const float* x, int64_t n, int k, int n_init, uint64_t seed
  * cluster among np.unique(used centres as value dtype: float64 if value_f64,
  * else float32) -- the GZIPTransformer input.  Host outputs (any may be NULL):
  * centres / counts / uniq [ntensors * k] (sorted), inertia / nuniq [ntensors].
- * Deterministic (integer atomics, fixed-order reductions); one sync at the end. */
+ * Deterministic (integer atomics, fixed-order reductions); one sync at the end.
+ * A tensor that holds a NaN or an infinity: OFL_EINVAL ("non-finite input"). */
 size_t ofl_kmeans1d_batch_workspace_bytes(int ntensors, const int64_t* numels);
 int ofl_kmeans1d_batch(int ntensors, const float* x_arena, const int64_t* offsets, const int64_t* numels, int k,
                        int n_init, uint64_t seed, int max_exact, int value_f64, float* ranks_out, double* centres,

@@ -213,6 +213,8 @@ struct BkmState {
     uint32_t mm[2];          // ~key(min), key(max): both reduced by atomicMax from 0
     int32_t converged;       // 0 running, 2 final assignment pass pending, 1 done
     int32_t nuniq;
+    int32_t has_nan;         // k_bkm_minmax met a NaN (min / max drop it)
+    int32_t pad_;
     double cen[kMaxK];       // sorted centres
     float mids[kMaxK];       // float32 midpoints of consecutive centres (+inf beyond k-1)
     float rank[kMaxK];       // float32 rank of each cluster's value
@@ -274,9 +276,11 @@ __global__ __launch_bounds__(kNT) void k_bkm_minmax(BkmArgs a) {
     int t; int64_t i0, i1;
     bkm_range(a, t, i0, i1);
     float lo = INFINITY, hi = -INFINITY;
-    bkm_visit(a.x + a.td[t].off, i0, i1, [&](float v) { lo = fminf(lo, v); hi = fmaxf(hi, v); });
+    bool nan = false;  // fminf / fmaxf drop a NaN: flagged apart, for the host to refuse
+    bkm_visit(a.x + a.td[t].off, i0, i1, [&](float v) { lo = fminf(lo, v); hi = fmaxf(hi, v); nan = nan || v != v; });
     lo = wave_min(lo);
     hi = wave_max(hi);
+    if (__any(nan) && (threadIdx.x & 63) == 0) atomicOr(&a.st[t].has_nan, 1);
     if ((threadIdx.x & 63) == 0) { rlo[threadIdx.x >> 6] = lo; rhi[threadIdx.x >> 6] = hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -586,8 +590,13 @@ __global__ __launch_bounds__(64) void k_bkm_pick(BkmArgs a) {
 }
 
 // exact Lloyd statistics: per block, cumulative count / sum / sum of squares
-// above each of the KM1 midpoints (+ totals); float per thread, double across
+// above each of the KM1 midpoints (+ totals); float per thread, double across.
+// The sums are of d = v - pivot of v's cluster (its current centre in
+// float32), not of v: d is as small as the cluster is wide, so the float sums
+// and k_bkm_update's variance, inertia and centres (pivot + mean of d) lose
+// nothing to the tensor's mean or to the distance between clusters.
 constexpr int kBkmAccNT = 1024;  // VALU-heavy per element: 16 waves per block
+DEVI float bkm_pivot(const BkmState& S, int j) { return (float)S.cen[j]; }
 template <int KM1>
 __global__ __launch_bounds__(kBkmAccNT) void k_bkm_acc(BkmArgs a) {
     constexpr int NV = KM1 + 1;
@@ -596,28 +605,37 @@ __global__ __launch_bounds__(kBkmAccNT) void k_bkm_acc(BkmArgs a) {
     bkm_range(a, t, i0, i1);
     const BkmState& S = a.st[t];
     if (S.converged == 1) return;
-    float m[KM1];
+    float m[KM1], p[NV];
 #pragma unroll
     for (int j = 0; j < KM1; ++j) m[j] = S.mids[j];
-    uint32_t n[NV];
-    float s[NV], q[NV];
 #pragma unroll
-    for (int j = 0; j < NV; ++j) { n[j] = 0; s[j] = 0.f; q[j] = 0.f; }
+    for (int j = 0; j < NV; ++j) p[j] = bkm_pivot(S, j);
+    // (d, d^2) of an element go into the pair sq[j] by one packed fma with
+    // g = 1.0f or 0.0f: the sums a select of d or 0 would give, bit for bit
+    // (a thread adds at most kBkmChunk / kBkmAccNT = 64 ones into n: exact)
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    float n[NV];
+    f2 sq[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) { n[j] = 0.f; sq[j] = f2{0.f, 0.f}; }
     bkm_visit<kBkmAccNT>(a.x + a.td[t].off, i0, i1, [&](float v) {
-        const float vv = v * v;
-        n[0] += 1; s[0] += v; q[0] += vv;
+        float pv = p[0];
+#pragma unroll
+        for (int j = 0; j < KM1; ++j) pv = v > m[j] ? p[j + 1] : pv;
+        const float d = v - pv;
+        const f2 e = {d, d * d};
+        n[0] += 1.f; sq[0] += e;
 #pragma unroll
         for (int j = 0; j < KM1; ++j) {
-            const bool g = v > m[j];
-            n[j + 1] += g ? 1u : 0u;
-            s[j + 1] += g ? v : 0.f;
-            q[j + 1] += g ? vv : 0.f;
+            const float g = v > m[j] ? 1.f : 0.f;
+            n[j + 1] += g;
+            sq[j + 1] = __builtin_elementwise_fma(e, f2{g, g}, sq[j + 1]);
         }
     });
     const int w = threadIdx.x >> 6;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
-        const double dn = wave_sum((double)n[j]), ds = wave_sum((double)s[j]), dq = wave_sum((double)q[j]);
+        const double dn = wave_sum((double)n[j]), ds = wave_sum((double)sq[j].x), dq = wave_sum((double)sq[j].y);
         if ((threadIdx.x & 63) == 0) { red[w][0][j] = dn; red[w][1][j] = ds; red[w][2][j] = dq; }
     }
     __syncthreads();
@@ -650,14 +668,25 @@ __global__ __launch_bounds__(64) void k_bkm_update(BkmArgs a) {
     double cg[kMaxK + 1], sg[kMaxK + 1], qg[kMaxK + 1];
     for (int j = 0; j < k; ++j) { cg[j] = g[0][j]; sg[j] = g[1][j]; qg[j] = g[2][j]; }
     cg[k] = 0.0; sg[k] = 0.0; qg[k] = 0.0;
-    // cluster j = (mid[j-1], mid[j]]: cumulative differences
+    // cluster j = (mid[j-1], mid[j]]: cumulative differences; Sm and Q are
+    // sums of v - pivot[j] (k_bkm_acc)
     double N[kMaxK], Sm[kMaxK], Q[kMaxK], nc[kMaxK];
+    double mean = 0.0;
     for (int j = 0; j < k; ++j) {
         N[j] = cg[j] - cg[j + 1];
         Sm[j] = sg[j] - sg[j + 1];
         Q[j] = qg[j] - qg[j + 1];
-        nc[j] = N[j] > 0 ? Sm[j] / N[j] : S.cen[j];
+        nc[j] = N[j] > 0 ? (double)bkm_pivot(S, j) + Sm[j] / N[j] : S.cen[j];
+        mean += N[j] * (double)bkm_pivot(S, j) + Sm[j];
     }
+    mean /= cg[0];
+    // the data's variance about its mean, cluster by cluster
+    double var = 0.0;
+    for (int j = 0; j < k; ++j) {
+        const double e = (double)bkm_pivot(S, j) - mean;
+        var += Q[j] + 2 * e * Sm[j] + e * e * N[j];
+    }
+    var /= cg[0];
     // sort the new centres with their statistics
     for (int i = 1; i < k; ++i) {
         const double v = nc[i], vn = N[i], vs = Sm[i], vq = Q[i];
@@ -670,8 +699,7 @@ __global__ __launch_bounds__(64) void k_bkm_update(BkmArgs a) {
     // sklearn's stopping rule: sum of squared centre shifts <= 1e-4 x the
     // data variance; then one more assignment pass with the final centres
     // (converged = 2) so that labels, counts and inertia belong to them
-    const double mean = sg[0] / cg[0];
-    const double tol = 1e-4 * fmax(qg[0] / cg[0] - mean * mean, 0.0);
+    const double tol = 1e-4 * fmax(var, 0.0);
     double shift = 0.0;
     for (int j = 0; j < k; ++j) shift += (nc[j] - S.cen[j]) * (nc[j] - S.cen[j]);
     const bool pending = S.converged == 2;
@@ -687,7 +715,7 @@ __global__ __launch_bounds__(64) void k_bkm_update(BkmArgs a) {
         bkm_set_centres(S, nc, k);
     } else {  // keep the centres the assignment was made with
         for (int j = 0; j < k; ++j) {  // (statistics above are sorted by new centre: redo by cluster)
-            const double c = S.cen[j];
+            const double c = S.cen[j] - (double)bkm_pivot(S, j);
             N[j] = cg[j] - cg[j + 1]; Sm[j] = sg[j] - sg[j + 1]; Q[j] = qg[j] - qg[j + 1];
             in += Q[j] - 2 * c * Sm[j] + c * c * N[j];
         }
@@ -1316,7 +1344,8 @@ int ofl_kmeans1d_batch_tab(int ntensors, const float* x_arena, const int64_t* of
     LHIP(hipStreamSynchronize(st));
     for (int t = 0; t < ntensors; ++t) {
         const float lo = unkey(~sh[t].mm[0]), hi = unkey(sh[t].mm[1]);
-        if (!std::isfinite(lo) || !std::isfinite(hi)) return lfail(OFL_EINVAL, "kmeans: non-finite input");
+        if (!std::isfinite(lo) || !std::isfinite(hi) || sh[t].has_nan)
+            return lfail(OFL_EINVAL, "kmeans: non-finite input");
         for (int j = 0; j < k; ++j) {
             if (centres) centres[(int64_t)t * k + j] = sh[t].cen[j];
             if (counts) counts[(int64_t)t * k + j] = sh[t].cnt[j];

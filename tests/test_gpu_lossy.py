@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from tests import golden_io
+from tests.kmeans_ref import kmeans_ref
 
 pytestmark = pytest.mark.gpu
 ARR, IDX = golden_io.lossy()
@@ -188,6 +189,9 @@ def test_kmeans_batch_vs_sklearn_and_deterministic():
         used = cen32[cnt[t] > 0]
         near = np.argmin(np.abs(x.astype(np.float64)[:, None] - used.astype(np.float64)[None, :]), axis=1)
         assert np.mean(uniq[t][r] == used[near]) >= 0.9999
+        exact = kmeans_ref(x, c[t], False)       # the labelling contract, element by element
+        np.testing.assert_array_equal(rk[o:o + x.size], exact.ranks)
+        np.testing.assert_array_equal(cnt[t], exact.count)
         ours = _inertia(x, uniq[t])
         if np.unique(x).size > 6:
             np.random.seed(t)
