@@ -161,7 +161,7 @@ int ofl_eden_decode(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uin
  * base_arena (nullable) and delta_arena share the plan's layout) instead of
  * reading a delta arena -- the delta's 8 B/element round trip through HBM
  * is not made.  Slices of at most 2^15 elements still read delta_arena, so
- * the caller fills it for their ranges (ofl_wavg_delta_ranges32).  Outputs
+ * the caller fills it for their ranges (ofl_wavg_delta32_ranges).  Outputs
  * equal ofl_eden_encode of the delta ofl_wavg_delta would write. */
 int ofl_eden_encode_wavg(ofl_eden_plan_t plan, const float* const* collab_arenas, const double* weights,
                          int ncollab, double wsum, const float* base_arena, const float* delta_arena,
@@ -371,13 +371,6 @@ int ofl_lut_decode_batch(int ntensors, const float* in_arena, const int64_t* off
  *                 (required as running sums when ncollab > 16), delta64_out
  *                 float64 delta, delta32_out the delta rounded to float32 (the
  *                 codec input, Eden.compress :579).
- * ofl_wavg_delta_ranges  the float64 delta at listed element ranges (host
- *                 starts/counts; single[r] != 0: a single-element tensor,
- *                 pairwise order as below), packed into out (device) -- the
- *                 values the Eden seed's serial sums read.  Synchronous.
- * ofl_wavg_delta_range_sums  the same ranges, each summed left to right in
- *                 float64 on the device (Python's sum() of the seed formula,
- *                 eden_pipeline.py:771); sums: host [nranges].  Synchronous.
  * ofl_wavg_delta_points  recompute listed elements (host idx) the way NumPy
  *                 reduces a single-element tensor's (C, 1) stack: pairwise
  *                 sum of the C products (1 <= ncollab <= 2048);
@@ -389,17 +382,12 @@ int ofl_lut_decode_batch(int ntensors, const float* in_arena, const int64_t* off
 const char* ofl_agg_last_error(void);
 int ofl_wavg_delta(int ncollab, const float* const* xs, const double* weights, double wsum, const float* base,
                    int64_t n, double* agg_out, double* delta64_out, float* delta32_out, void* stream);
-size_t ofl_wavg_ranges_workspace_bytes(int ncollab, int nranges);
-int ofl_wavg_delta_ranges(int ncollab, const float* const* xs, const double* weights, double wsum,
-                          const float* base, int nranges, const int64_t* starts, const int64_t* counts,
-                          const int32_t* single, double* out, void* ws, size_t ws_bytes, void* stream);
-size_t ofl_wavg_range_sums_workspace_bytes(int ncollab, int nranges, int64_t total);
-int ofl_wavg_delta_range_sums(int ncollab, const float* const* xs, const double* weights, double wsum,
-                              const float* base, int nranges, const int64_t* starts, const int64_t* counts,
-                              const int32_t* single, double* sums, void* ws, size_t ws_bytes, void* stream);
 /* ofl_wavg_delta_seeds  the Eden seeds of a round end without a host round
  *                 trip: the float64 delta on the listed ranges (packed_dev,
- *                 total doubles), their left-to-right sums (sums_dev), and
+ *                 total doubles; single_dev[r] != 0: a single-element tensor,
+ *                 pairwise order as ofl_wavg_delta_points), their
+ *                 left-to-right float64 sums (sums_dev; Python's sum() of the
+ *                 seed formula, eden_pipeline.py:771), and
  *                 seeds_dev[r] = (hash(sum*13 + 7) + draws_dev[r]) % 2^16 with
  *                 CPython's float hash (eden_pipeline.py:771-772).  Every
  *                 pointer is DEVICE memory (xs_dev: ncollab pointers,

@@ -30,6 +30,7 @@ AdagradAdaptiveAggregation (core/adaptive_aggregation.py on
 utilities/optimizers/numpy/*_optimizer.py), whose parameters and moments stay
 on the device between rounds (ofl_adaptive_step).
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -45,6 +46,20 @@ _ROW_TILE = 1 << 15  # slices above this go through the row passes (kRowLog)
 
 def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def _ptr(t):
+    """A device tensor's address, None (NULL) for an absent one."""
+    return t.data_ptr() if t is not None else None
+
+
+def _ptrs(xs):
+    """The host pointer table of device tensors; keep it alive across the call."""
+    return np.asarray([x.data_ptr() for x in xs], np.uint64)
+
+
+def _flat_to(arrs, device):
+    return [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(device) for a in arrs]
 
 
 def _f64_weights(weights, n):
@@ -65,24 +80,48 @@ def weight_sum(weights, ndim):
     return float(np.asarray(scl).reshape(-1)[0])
 
 
+def _f32_stack(name, tensors):
+    arrs = [np.asarray(t) for t in tensors]
+    if not arrs:
+        raise _lib.CodecError(f"{name}: no tensors")
+    shape = arrs[0].shape
+    if any(a.shape != shape or a.dtype != np.float32 for a in arrs):
+        raise _lib.CodecError(f"{name}: float32 tensors of one shape")
+    return arrs, shape, int(np.prod(shape, dtype=np.int64))
+
+
+def _check_collaborators(name, n, limit):
+    if n > limit:
+        raise _lib.CodecError(f"{name}: {n} collaborators, at most {limit} are supported")
+
+
+class _Plugin:
+    """What the AggregationFunction plugins share: __call__ -> call(local_tensors,
+    ...) and, for the stateless ones, a constructor that takes the device."""
+
+    def __init__(self, device=None):
+        self.device = device
+
+    def __call__(self, local_tensors, *args):
+        return self.call(local_tensors, *args)
+
+
 def _wavg_launch(xs, w64, wsum, base, n, agg=None, delta64=None, delta32=None, device=None):
-    ptrs = np.asarray([x.data_ptr() for x in xs], np.uint64)
+    ptrs = _ptrs(xs)
     _lib.check_agg(_lib.lib().ofl_wavg_delta(
-        len(xs), ptrs.ctypes.data, w64.ctypes.data, wsum, base.data_ptr() if base is not None else None, int(n),
-        agg.data_ptr() if agg is not None else None, delta64.data_ptr() if delta64 is not None else None,
-        delta32.data_ptr() if delta32 is not None else None, _stream(device)))
+        len(xs), ptrs.ctypes.data, w64.ctypes.data, wsum, _ptr(base), int(n), _ptr(agg), _ptr(delta64), _ptr(delta32),
+        _stream(device)))
 
 
 def _points_launch(xs, w64, wsum, base, idx, agg, delta32, device, ws):
-    ptrs = np.asarray([x.data_ptr() for x in xs], np.uint64)
+    ptrs = _ptrs(xs)
     ix = np.ascontiguousarray(idx, np.int64)
     L = _lib.lib()
     need = int(L.ofl_wavg_points_workspace_bytes(len(xs), ix.size))
     buf = ws(need)
     _lib.check_agg(L.ofl_wavg_delta_points(
-        len(xs), ptrs.ctypes.data, w64.ctypes.data, wsum, base.data_ptr() if base is not None else None, ix.size,
-        ix.ctypes.data, agg.data_ptr() if agg is not None else None, None,
-        delta32.data_ptr() if delta32 is not None else None, buf.data_ptr(), buf.numel(), _stream(device)))
+        len(xs), ptrs.ctypes.data, w64.ctypes.data, wsum, _ptr(base), ix.size, ix.ctypes.data, _ptr(agg), None,
+        _ptr(delta32), buf.data_ptr(), buf.numel(), _stream(device)))
 
 
 class _Scratch:
@@ -100,19 +139,13 @@ def weighted_average(tensors, weights, device=None):
     """np.average(tensors, weights=weights, axis=0) on the GPU
     (weighted_average.py:12-14): float32 tensors, float64 result, bit-exact."""
     dev = resolve_device(device)
-    arrs = [np.asarray(t) for t in tensors]
-    if not arrs:
-        raise _lib.CodecError("weighted_average: no tensors")
-    shape = arrs[0].shape
-    if any(a.shape != shape or a.dtype != np.float32 for a in arrs):
-        raise _lib.CodecError("weighted_average: float32 tensors of one shape")
+    arrs, shape, n = _f32_stack("weighted_average", tensors)
     w64 = _f64_weights(weights, len(arrs))
     wsum = weight_sum(w64, len(shape))
     if wsum == 0.0:
         raise ZeroDivisionError("Weights sum to zero, can't be normalized")
-    n = int(np.prod(shape, dtype=np.int64))
     with torch.cuda.device(dev):
-        xs = [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev) for a in arrs]
+        xs = _flat_to(arrs, dev)
         agg = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
         if n == 1:
             _points_launch(xs, w64, wsum, None, [0], agg, None, dev, _Scratch(dev))
@@ -121,19 +154,13 @@ def weighted_average(tensors, weights, device=None):
         return agg[:n].cpu().numpy().reshape(shape)
 
 
-class WeightedAverage:
+class WeightedAverage(_Plugin):
     """AggregationFunction plugin (weighted_average.py:17-58): call(local_tensors, ...)
     -> np.average of the LocalTensor tensors by their weights, on the GPU."""
-
-    def __init__(self, device=None):
-        self.device = device
 
     def call(self, local_tensors, *_):
         tensors, weights = zip(*[(x.tensor, x.weight) for x in local_tensors])
         return weighted_average(tensors, weights, self.device)
-
-    def __call__(self, local_tensors, *args):
-        return self.call(local_tensors, *args)
 
 
 _MEDIAN_MAX_C = 128   # ofl_median_delta: <= 16 in registers, <= 128 through LDS
@@ -143,28 +170,11 @@ _GM_CHUNK_DT = np.dtype([("start", "<i8"), ("len", "<i4"), ("tensor", "<i4")])  
 AGGREGATIONS = ("weighted_average", "median", "geometric_median")
 
 
-def _f32_stack(name, tensors):
-    arrs = [np.asarray(t) for t in tensors]
-    if not arrs:
-        raise _lib.CodecError(f"{name}: no tensors")
-    shape = arrs[0].shape
-    if any(a.shape != shape or a.dtype != np.float32 for a in arrs):
-        raise _lib.CodecError(f"{name}: float32 tensors of one shape")
-    return arrs, shape, int(np.prod(shape, dtype=np.int64))
-
-
-def _check_collaborators(name, n, limit):
-    if n > limit:
-        raise _lib.CodecError(f"{name}: {n} collaborators, at most {limit} are supported")
-
-
 def _median_launch(xs, base, n, med=None, delta=None, device=None):
     _check_collaborators("median", len(xs), _MEDIAN_MAX_C)
-    ptrs = np.asarray([x.data_ptr() for x in xs], np.uint64)
+    ptrs = _ptrs(xs)
     _lib.check_agg(_lib.lib().ofl_median_delta(
-        len(xs), ptrs.ctypes.data, base.data_ptr() if base is not None else None, int(n),
-        med.data_ptr() if med is not None else None, delta.data_ptr() if delta is not None else None,
-        _stream(device)))
+        len(xs), ptrs.ctypes.data, _ptr(base), int(n), _ptr(med), _ptr(delta), _stream(device)))
 
 
 def median(tensors, device=None):
@@ -177,24 +187,17 @@ def median(tensors, device=None):
     with torch.cuda.device(dev):
         out = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
         if n:
-            xs = [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev) for a in arrs]
-            _median_launch(xs, None, n, med=out, device=dev)
+            _median_launch(_flat_to(arrs, dev), None, n, med=out, device=dev)
         return out[:n].cpu().numpy().reshape(shape)
 
 
-class Median:
+class Median(_Plugin):
     """AggregationFunction plugin (median.py:12-49): call(local_tensors, ...) ->
     np.median of the LocalTensor tensors on the GPU; the weights are ignored,
     as in the reference."""
 
-    def __init__(self, device=None):
-        self.device = device
-
     def call(self, local_tensors, *_):
         return median([x.tensor for x in local_tensors], self.device)
-
-    def __call__(self, local_tensors, *args):
-        return self.call(local_tensors, *args)
 
 
 def _gm_start_weights(weights, n):
@@ -239,12 +242,10 @@ class _GmLayout:
 
     def launch(self, xs, w0, maxiter, eps, ftol, base, agg=None, delta64=None, delta32=None, device=None):
         _check_collaborators("geometric_median", len(xs), _GMEDIAN_MAX_C)
-        ptrs = np.asarray([x.data_ptr() for x in xs], np.uint64)
+        ptrs = _ptrs(xs)
         _lib.check_agg(_lib.lib().ofl_gmedian_delta(
-            len(xs), ptrs.ctypes.data, w0.ctypes.data, int(maxiter), float(eps), float(ftol),
-            base.data_ptr() if base is not None else None, self.ntensors, self.chunks.data_ptr(), self.nchunks,
-            self.first.data_ptr(), agg.data_ptr() if agg is not None else None,
-            delta64.data_ptr() if delta64 is not None else None, delta32.data_ptr() if delta32 is not None else None,
+            len(xs), ptrs.ctypes.data, w0.ctypes.data, int(maxiter), float(eps), float(ftol), _ptr(base), self.ntensors,
+            self.chunks.data_ptr(), self.nchunks, self.first.data_ptr(), _ptr(agg), _ptr(delta64), _ptr(delta32),
             self.iters.data_ptr(), self.ws.data_ptr(), self.ws.numel(), _stream(device)))
 
 
@@ -261,28 +262,21 @@ def geometric_median(tensors, weights, maxiter=4, eps=1e-5, ftol=1e-6, device=No
     w0 = _gm_start_weights(weights, len(arrs))
     with torch.cuda.device(dev):
         lay = _GmLayout([0], [n], dev)
-        xs = [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev) if n else
-              torch.zeros(1, dtype=torch.float32, device=dev) for a in arrs]
+        xs = _flat_to(arrs, dev) if n else [torch.zeros(1, dtype=torch.float32, device=dev) for _ in arrs]
         agg = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
         lay.launch(xs, w0, maxiter, eps, ftol, None, agg=agg, device=dev)
         res = agg[:n].cpu().numpy().reshape(shape)
         return (res, int(lay.iters[0].item())) if return_iterations else res
 
 
-class GeometricMedian:
+class GeometricMedian(_Plugin):
     """AggregationFunction plugin (geometric_median.py:76-112): call(local_tensors,
     ...) -> geometric_median of the LocalTensor tensors by their weights, on the
     GPU (the reference's defaults: maxiter 4, eps 1e-5, ftol 1e-6)."""
 
-    def __init__(self, device=None):
-        self.device = device
-
     def call(self, local_tensors, *_):
         tensors, weights = zip(*[(x.tensor, x.weight) for x in local_tensors])
         return geometric_median(tensors, np.array(weights), device=self.device)
-
-    def __call__(self, local_tensors, *args):
-        return self.call(local_tensors, *args)
 
 
 # ---- FedOpt server optimisers (core/adaptive_aggregation.py:38-113 on
@@ -370,17 +364,15 @@ def adaptive_step(hyper, steps_taken, xs, weights32, base, n, p, m, v, agg_out=N
     _check_collaborators(hyper.kind, len(xs), _ADAPTIVE_MAX_C)
     if len(xs) < 1 or len(weights32) != len(xs):
         raise _lib.CodecError(f"{hyper.kind}: one float32 weight per collaborator tensor, at least one")
-    ptrs = np.asarray([x.data_ptr() for x in xs], np.uint64)
+    ptrs = _ptrs(xs)
     w32 = np.ascontiguousarray(weights32, np.float32)
     k = hyper.consts(steps_taken)
     _lib.check_agg(_lib.lib().ofl_adaptive_step(
-        len(xs), ptrs.ctypes.data, w32.ctypes.data, base.data_ptr(), int(n), p.data_ptr(),
-        m.data_ptr() if m is not None else None, v.data_ptr(), ctypes.addressof(k),
-        agg_out.data_ptr() if agg_out is not None else None, delta_out.data_ptr() if delta_out is not None else None,
-        _stream(device)))
+        len(xs), ptrs.ctypes.data, w32.ctypes.data, base.data_ptr(), int(n), p.data_ptr(), _ptr(m), v.data_ptr(),
+        ctypes.addressof(k), _ptr(agg_out), _ptr(delta_out), _stream(device)))
 
 
-class _AdaptiveAggregation:
+class _AdaptiveAggregation(_Plugin):
     """AdaptiveAggregation (core/adaptive_aggregation.py:16-113) with the
     optimiser's state on the device.  params: dict name -> float32 array, the
     parameters the optimiser owns (copied to the device; unlike the reference
@@ -459,14 +451,11 @@ class _AdaptiveAggregation:
         p = self._p[tensor_name]
         with torch.cuda.device(dev):
             if n:
-                ts = [torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(dev) for a in arrs]
+                ts = _flat_to(arrs, dev)
                 adaptive_step(self.hyper, self.current_step[tensor_name], ts[:-1], w32, ts[-1], n, p,
                               self._m[tensor_name], self._v[tensor_name], device=dev)
             self.current_step[tensor_name] += 1
             return p.cpu().numpy().reshape(shape)
-
-    def __call__(self, local_tensors, *args):
-        return self.call(local_tensors, *args)
 
 
 class AdamAdaptiveAggregation(_AdaptiveAggregation):
@@ -487,6 +476,30 @@ class AdagradAdaptiveAggregation(_AdaptiveAggregation):
     params, agg_func=WeightedAverage(), learning_rate=0.01,
     initial_accumulator_value=0.1, epsilon=1e-10, device=None); no betas."""
     kind = "adagrad"
+
+
+class _RangeTable:
+    """Element ranges [(start, count)] of an arena as the device tables the
+    *_ranges and *_seeds entry points take: n ranges of `total` elements,
+    start [n] and dst [n + 1] (the exclusive prefix of the counts)."""
+
+    def __init__(self, ranges, device):
+        counts = [c for _, c in ranges]
+        self.n = len(ranges)
+        self.total = int(sum(counts))
+        self.start = torch.tensor([s for s, _ in ranges] or [0], dtype=torch.int64).to(device)
+        self.dst = torch.from_numpy(np.cumsum([0] + counts).astype(np.int64)).to(device)
+
+    @property
+    def args(self):
+        """(nranges, starts, dst, total), the order every entry point has them in."""
+        return self.n, self.start.data_ptr(), self.dst.data_ptr(), self.total
+
+
+# what RoundEnd._device_seeds sums: the weighted average's float64 delta, formed
+# again from the collaborators, or another aggregate's arena (float64: agg - base)
+_WavgSeeds = collections.namedtuple("_WavgSeeds", "w64 wsum fused")
+_AggSeeds = collections.namedtuple("_AggSeeds", "agg is_f64 base")
 
 
 class RoundEnd:
@@ -562,30 +575,24 @@ class RoundEnd:
         self._codec_ws = None
         # tensors the codec does not touch (small, <= dim_threshold): their
         # apply_delta runs on these ranges (device tables)
-        rest = [i for i in range(len(self.numels)) if i not in set(self.big) and self.numels[i] > 0]
-        self._rest_n = len(rest)
-        self._rest_total = sum(self.numels[i] for i in rest)
-        dst = np.cumsum([0] + [self.numels[i] for i in rest]).astype(np.int64)
-        self._rest_start = torch.tensor([self.offsets[i] for i in rest] or [0], dtype=torch.int64).to(self.device)
-        self._rest_dst = torch.from_numpy(dst).to(self.device)
+        rest = [(self.offsets[i], n) for i, n in enumerate(self.numels) if 0 < n <= self.dim_threshold]
+        self._rest = _RangeTable(rest, self.device)
         # seed ranges (a prefix per tensor in fast mode, all of it in reference
         # mode) as device tables: the seeds are computed without a host round trip
         T = len(self.numels)
         counts = [min(n, _FAST_SEED_PREFIX) if self.seed_mode == "fast" else n for n in self.numels]
-        self._seed_total = int(sum(counts))
-        self._seed_start = torch.tensor(self.offsets or [0], dtype=torch.int64).to(self.device)
-        self._seed_dst = torch.from_numpy(np.cumsum([0] + counts).astype(np.int64)).to(self.device)
+        self._seed = _RangeTable(list(zip(self.offsets, counts)), self.device)
         self._seed_single = torch.tensor([1 if n == 1 else 0 for n in self.numels] or [0], dtype=torch.int32).to(self.device)
         self._seed_sums = torch.empty(max(T, 1), dtype=torch.float64, device=self.device)
         self._seeds = torch.empty(max(T, 1), dtype=torch.int32, device=self.device)
-        self._packed = torch.empty(max(self._seed_total, 1), dtype=torch.float64, device=self.device)
+        self._packed = torch.empty(max(self._seed.total, 1), dtype=torch.float64, device=self.device)
         self._big_idx = torch.tensor(self.big or [0], dtype=torch.int64).to(self.device)
         # fused round-end encode (ofl_eden_encode_wavg): the large slices' row
         # pass computes the delta from the collaborators' arenas itself, so the
         # delta arena is written only where something else reads it -- the
         # tensors the codec does not touch and the slices of <= 2^15 elements
         self.fused = bool(fused) and self.plan is not None and aggregation == "weighted_average"
-        fz = [(self.offsets[i], self.numels[i]) for i in rest]
+        fz = list(rest)
         for t, i in enumerate(self.big):
             _, lens = slice_plan(self.numels[i])
             xo = self.offsets[i]
@@ -593,14 +600,9 @@ class RoundEnd:
                 if P <= _ROW_TILE and ln > 0:
                     fz.append((xo, ln))
                 xo += ln
-        fz.sort()
-        self._fz_n = len(fz)
-        self._fz_total = sum(n for _, n in fz)
-        self._fz_start = torch.tensor([o for o, _ in fz] or [0], dtype=torch.int64).to(self.device)
-        self._fz_dst = torch.from_numpy(np.cumsum([0] + [n for _, n in fz]).astype(np.int64)).to(self.device)
-        self._host_args = None   # pinned [collaborator pointers | weights | draws], reused after _args_done
-        self._dev_args = None
-        self._args_done = None
+        self._fz = _RangeTable(sorted(fz), self.device)
+        # pinned [collaborator pointers | weights | draws], reused after _args_done, and its device copy
+        self._host_args = self._dev_args = self._args_done = None
         # geometric median: the chunk table of this layout, per-tensor state and
         # (without agg_out) the float64 aggregate the delta and seeds come from
         self._gm = _GmLayout(self.offsets, self.numels, self.device) if aggregation == "geometric_median" else None
@@ -628,11 +630,9 @@ class RoundEnd:
         and second moment filled with initial_accumulator_value, no steps taken."""
         if self.aggregation not in ADAPTIVE_AGGREGATIONS:
             raise _lib.CodecError(f"aggregation {self.aggregation!r} has no optimizer")
-        x = params_arena
-        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= self.arena_numel):
-            raise _lib.CodecError("arenas must be contiguous float32 device tensors of arena_numel elements")
+        self._check_arena(params_arena)
         with torch.cuda.device(self.device):
-            p = x[:self.arena_numel].to(self.device, copy=True)
+            p = params_arena[:self.arena_numel].to(self.device, copy=True)
             acc = self._hyper.initial_accumulator_value
             m = torch.full_like(p, acc) if self.aggregation != "adagrad" else None
             self._opt = (p, m, torch.full_like(p, acc))
@@ -669,120 +669,124 @@ class RoundEnd:
         -> (new model arena, [(payload bytes, [metadata])] per tensor or None,
         seeds: a list with payloads, else the device int32 tensor -- without
         payloads nothing synchronises with the host)."""
-        dev = self.device
         xs = list(collab_arenas)
         for x in xs + ([base_arena] if base_arena is not None else []):
-            if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= self.arena_numel):
-                raise _lib.CodecError("arenas must be contiguous float32 device tensors of arena_numel elements")
+            self._check_arena(x)
         f32_agg = self.aggregation == "median" or self.aggregation in ADAPTIVE_AGGREGATIONS
         agg_dtype = torch.float32 if f32_agg else torch.float64
         if agg_out is not None and not (agg_out.dtype == agg_dtype and agg_out.numel() >= self.arena_numel):
             raise _lib.CodecError(f"agg_out must be {str(agg_dtype)[6:]} with arena_numel elements")
-        if self.aggregation != "weighted_average":
-            return self._run_robust(xs, weights, base_arena, agg_out, payloads, out)
+        family = self.aggregation if self.aggregation in AGGREGATIONS else "adaptive"
+        with torch.cuda.device(self.device):
+            # 1. the aggregate and its delta rounded to float32, by the aggregation's kernels
+            delta, seed_source = getattr(self, "_delta_" + family)(xs, weights, base_arena, agg_out)
+            # 2. the seeds, 3. encode, (payloads), decode in place, apply
+            wavg = self._device_seeds(seed_source, xs, base_arena)
+            return self._encode_apply(delta, base_arena, payloads, out, wavg)
+
+    def _check_arena(self, x):
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= self.arena_numel):
+            raise _lib.CodecError("arenas must be contiguous float32 device tensors of arena_numel elements")
+
+    def _empty_arena(self):
+        return torch.empty(self.arena_numel, dtype=torch.float32, device=self.device)
+
+    # -- step 1 of run() per family -> (float32 delta arena, the seeds' source); all raise before the draws --
+    def _delta_weighted_average(self, xs, weights, base_arena, agg_out):
+        """average + delta in float64, the delta rounded to float32 -- fused:
+        only on the ranges the large slices' encode does not compute."""
+        dev = self.device
         w64 = _f64_weights(weights, len(xs))
         wsum = self._wsum(w64)
-        L = _lib.lib()
         fused = self.fused and agg_out is None and len(xs) <= 16
-        with torch.cuda.device(dev):
-            delta = torch.empty(self.arena_numel, dtype=torch.float32, device=dev)
-            if agg_out is None and len(xs) > 16:  # running sums between chained launches
-                agg_out = torch.empty(self.arena_numel, dtype=torch.float64, device=dev)
-            # 1. average + delta (float64), delta rounded to float32 -- fused:
-            # only on the ranges the large slices' encode does not compute
-            if fused:
-                ptrs = np.asarray([x.data_ptr() for x in xs], np.uint64)
-                _lib.check_agg(L.ofl_wavg_delta32_ranges(
-                    len(xs), ptrs.ctypes.data, w64.ctypes.data, wsum,
-                    base_arena.data_ptr() if base_arena is not None else None, self._fz_n,
-                    self._fz_start.data_ptr(), self._fz_dst.data_ptr(), self._fz_total, delta.data_ptr(),
-                    _stream(dev)))
-            else:
-                _wavg_launch(xs, w64, wsum, base_arena, self.arena_numel, agg=agg_out, delta32=delta, device=dev)
-            if self.single:
-                _points_launch(xs, w64, wsum, base_arena, [self.offsets[i] for i in self.single], agg_out, delta,
-                               dev, self._ws)
-            # 2. seeds on the device: serial sums of the float64 delta, CPython's
-            # float hash, one np.random draw per tensor in order (drawn here)
-            T = len(self.numels)
-            C = len(xs)
-            draws = np.random.randint(1, 2 ** 16, size=T).astype(np.int64) if T else np.zeros(0, np.int64)
-            dp = self._stage_args([np.asarray([x.data_ptr() for x in xs], np.uint64).view(np.int64),
-                                   w64.view(np.int64), draws])
-            _lib.check_agg(L.ofl_wavg_delta_seeds(
-                C, dp, dp + 8 * C, wsum, base_arena.data_ptr() if base_arena is not None else None, T,
-                self._seed_start.data_ptr(), self._seed_dst.data_ptr(), self._seed_single.data_ptr(), self._seed_total,
-                dp + 16 * C, self._seeds.data_ptr(), self._seed_sums.data_ptr(), self._packed.data_ptr(), _stream(dev)))
-            return self._encode_apply(delta, base_arena, payloads, out, (dp, C, wsum) if fused else None)
+        delta = self._empty_arena()
+        if agg_out is None and len(xs) > 16:  # running sums between chained launches
+            agg_out = torch.empty(self.arena_numel, dtype=torch.float64, device=dev)
+        if fused:
+            ptrs = _ptrs(xs)
+            _lib.check_agg(_lib.lib().ofl_wavg_delta32_ranges(
+                len(xs), ptrs.ctypes.data, w64.ctypes.data, wsum, _ptr(base_arena), *self._fz.args, delta.data_ptr(),
+                _stream(dev)))
+        else:
+            _wavg_launch(xs, w64, wsum, base_arena, self.arena_numel, agg=agg_out, delta32=delta, device=dev)
+        if self.single:
+            _points_launch(xs, w64, wsum, base_arena, [self.offsets[i] for i in self.single], agg_out, delta, dev,
+                           self._ws)
+        return delta, _WavgSeeds(w64, wsum, fused)
+
+    def _delta_median(self, xs, weights, base_arena, agg_out):
+        """elementwise over the whole arena; the float32 delta it writes is the
+        array the seed formula sums."""
+        delta = self._empty_arena()
+        _median_launch(xs, base_arena, self.arena_numel, med=agg_out, delta=delta, device=self.device)
+        return delta, _AggSeeds(delta, 0, None)
+
+    def _delta_geometric_median(self, xs, weights, base_arena, agg_out):
+        """Weiszfeld per tensor; the seeds come from generate_delta of the
+        float64 aggregate: agg - base in float64."""
+        _check_collaborators("geometric_median", len(xs), _GMEDIAN_MAX_C)
+        w0 = _gm_start_weights(weights, len(xs))
+        delta = self._empty_arena()
+        if agg_out is None:
+            if self._gm_agg is None:
+                self._gm_agg = torch.zeros(self.arena_numel, dtype=torch.float64, device=self.device)
+            agg_out = self._gm_agg
+        self._gm.launch(xs, w0, 4, 1e-5, 1e-6, base_arena, agg=agg_out, delta32=delta, device=self.device)
+        return delta, _AggSeeds(agg_out, 1, base_arena)
+
+    def _delta_adaptive(self, xs, weights, base_arena, agg_out):
+        """one elementwise step over the whole arena (in the alignment gaps
+        everything is zero: a zero gradient); the float32 delta it writes is
+        generate_delta of two float32 arrays."""
+        if self._opt is None:
+            raise _lib.CodecError(f"{self.aggregation}: call init_optimizer(params_arena) before run()")
+        if base_arena is None:
+            raise _lib.CodecError(f"{self.aggregation}: base_arena is required, the gradient is formed against it")
+        _check_collaborators(self.aggregation, len(xs), _ADAPTIVE_MAX_C)
+        if weights is None or len(weights) != len(xs) or not xs:
+            raise _lib.CodecError("one weight per collaborator tensor")
+        w32 = _f32_weights(self.aggregation, list(weights))
+        delta = self._empty_arena()
+        p, m, v = self._opt
+        adaptive_step(self._hyper, self._opt_step, xs, w32, base_arena, self.arena_numel, p, m, v, agg_out=agg_out,
+                      delta_out=delta, device=self.device)
+        self._opt_step += 1
+        return delta, _AggSeeds(delta, 0, None)
+
+    def _device_seeds(self, src, xs, base_arena):
+        """Step 2 of run(), into self._seeds without a host round trip: serial
+        sums of the delta on the seed ranges, CPython's float hash, one
+        np.random draw per tensor in order (drawn here).  -> (device args,
+        collaborators, weight sum) for the fused encode, else None."""
+        L = _lib.lib()
+        T, C = len(self.numels), len(xs)
+        draws = np.random.randint(1, 2 ** 16, size=T).astype(np.int64) if T else np.zeros(0, np.int64)
+        out = self._seeds.data_ptr(), self._seed_sums.data_ptr(), self._packed.data_ptr(), _stream(self.device)
+        if isinstance(src, _AggSeeds):
+            dp = self._stage_args([draws])
+            _lib.check_agg(L.ofl_agg_delta_seeds(src.agg.data_ptr(), src.is_f64, _ptr(src.base), *self._seed.args, dp,
+                                                 *out))
+            return None
+        dp = self._stage_args([_ptrs(xs).view(np.int64), src.w64.view(np.int64), draws])
+        _lib.check_agg(L.ofl_wavg_delta_seeds(
+            C, dp, dp + 8 * C, src.wsum, _ptr(base_arena), T, self._seed.start.data_ptr(), self._seed.dst.data_ptr(),
+            self._seed_single.data_ptr(), self._seed.total, dp + 16 * C, *out))
+        return (dp, C, src.wsum) if src.fused else None
 
     def _stage_args(self, parts):
         """int64 words (pointers, weight bits, draws) -> the device copy's
         address, through a pinned buffer that is reused once its copy has left."""
-        dev = self.device
         need = sum(len(p) for p in parts) + 1
         if self._host_args is None or self._host_args.numel() < need:
             self._host_args = torch.empty(need, dtype=torch.int64).pin_memory()
-            self._dev_args = torch.empty(need, dtype=torch.int64, device=dev)
+            self._dev_args = torch.empty(need, dtype=torch.int64, device=self.device)
             self._args_done = torch.cuda.Event()
         else:
             self._args_done.synchronize()  # the previous call's copy has left the pinned buffer
-        ha = self._host_args.numpy()
-        o = 0
-        for p in parts:
-            ha[o:o + len(p)] = p
-            o += len(p)
+        self._host_args.numpy()[:need - 1] = np.concatenate(parts)
         self._dev_args[:need].copy_(self._host_args[:need], non_blocking=True)
         self._args_done.record()
         return self._dev_args.data_ptr()
-
-    def _run_robust(self, xs, weights, base_arena, agg_out, payloads, out):
-        """run() for every aggregation but the weighted average: the delta
-        arena from their kernels, the seeds from that delta, then the shared tail."""
-        dev = self.device
-        L = _lib.lib()
-        T = len(self.numels)
-        if self.aggregation in ADAPTIVE_AGGREGATIONS:
-            if self._opt is None:
-                raise _lib.CodecError(f"{self.aggregation}: call init_optimizer(params_arena) before run()")
-            if base_arena is None:
-                raise _lib.CodecError(f"{self.aggregation}: base_arena is required, the gradient is formed against it")
-            _check_collaborators(self.aggregation, len(xs), _ADAPTIVE_MAX_C)
-            if weights is None or len(weights) != len(xs) or not xs:
-                raise _lib.CodecError("one weight per collaborator tensor")
-            weights = _f32_weights(self.aggregation, list(weights))
-        with torch.cuda.device(dev):
-            delta = torch.empty(self.arena_numel, dtype=torch.float32, device=dev)
-            if self.aggregation in ADAPTIVE_AGGREGATIONS:
-                # one elementwise step over the whole arena (in the alignment gaps
-                # everything is zero: a zero gradient); the float32 delta it
-                # writes is generate_delta of two float32 arrays
-                p, m, v = self._opt
-                adaptive_step(self._hyper, self._opt_step, xs, weights, base_arena, self.arena_numel, p, m, v,
-                              agg_out=agg_out, delta_out=delta, device=dev)
-                self._opt_step += 1
-                src, is_f64, seed_base = delta, 0, None
-            elif self.aggregation == "median":
-                # elementwise over the whole arena; the float32 delta it writes
-                # is the array the seed formula sums
-                _median_launch(xs, base_arena, self.arena_numel, med=agg_out, delta=delta, device=dev)
-                src, is_f64, seed_base = delta, 0, None
-            else:
-                _check_collaborators("geometric_median", len(xs), _GMEDIAN_MAX_C)
-                w0 = _gm_start_weights(weights, len(xs))
-                if agg_out is None:
-                    if self._gm_agg is None:
-                        self._gm_agg = torch.zeros(self.arena_numel, dtype=torch.float64, device=dev)
-                    agg_out = self._gm_agg
-                self._gm.launch(xs, w0, 4, 1e-5, 1e-6, base_arena, agg=agg_out, delta32=delta, device=dev)
-                # generate_delta of the float64 aggregate: agg - base in float64
-                src, is_f64, seed_base = agg_out, 1, base_arena
-            draws = np.random.randint(1, 2 ** 16, size=T).astype(np.int64) if T else np.zeros(0, np.int64)
-            dp = self._stage_args([draws])
-            _lib.check_agg(L.ofl_agg_delta_seeds(
-                src.data_ptr(), is_f64, seed_base.data_ptr() if seed_base is not None else None, T,
-                self._seed_start.data_ptr(), self._seed_dst.data_ptr(), self._seed_total, dp,
-                self._seeds.data_ptr(), self._seed_sums.data_ptr(), self._packed.data_ptr(), _stream(dev)))
-            return self._encode_apply(delta, base_arena, payloads, out, None)
 
     def _encode_apply(self, delta, base_arena, payloads, out, wavg):
         """run() from the seeds on: encode, payloads, decode fused with
@@ -795,11 +799,11 @@ class RoundEnd:
         if fused:
             dp, C, wsum = wavg
         with torch.cuda.device(dev):
-            seeds = None
-            if payloads:
-                seeds = [int(v) for v in self._seeds[:T].cpu().numpy()]
+            seeds = [int(v) for v in self._seeds[:T].cpu().numpy()] if payloads else None
             # 3. encode, (payloads), decode in place, apply
             result = [None] * len(self.numels) if payloads else None
+            if out is None:
+                out = self._empty_arena()
             if self.plan is not None:
                 p = self.plan
                 sd = self._seeds.index_select(0, self._big_idx)
@@ -809,9 +813,9 @@ class RoundEnd:
                     self._codec_ws = torch.empty(max(p.ws_bytes, 256), dtype=torch.uint8, device=dev)
                 if fused:
                     _lib.check(L.ofl_eden_encode_wavg(
-                        p.handle, dp, dp + 8 * C, C, wsum, base_arena.data_ptr() if base_arena is not None else None,
-                        delta.data_ptr(), sd.data_ptr(), planes.data_ptr(), scales.data_ptr(),
-                        self._codec_ws.data_ptr(), self._codec_ws.numel(), _stream(dev)))
+                        p.handle, dp, dp + 8 * C, C, wsum, _ptr(base_arena), delta.data_ptr(), sd.data_ptr(),
+                        planes.data_ptr(), scales.data_ptr(), self._codec_ws.data_ptr(), self._codec_ws.numel(),
+                        _stream(dev)))
                 else:
                     p.encode(delta, sd, planes, scales, self._codec_ws)
                 if payloads:
@@ -825,8 +829,6 @@ class RoundEnd:
                             md[3 + 2 * k] = float(d)
                         result[i] = (hostmem.bytes_from(pn.ctypes.data + po, pb), [{"int_list": list(self.shapes[i]), "int_to_float": md}])
                 if base_arena is not None:  # decode + apply_delta fused: out = base + decoded
-                    if out is None:
-                        out = torch.empty(self.arena_numel, dtype=torch.float32, device=dev)
                     p.decode(planes, sd, scales, out, self._codec_ws, base=base_arena)
                 else:
                     p.decode(planes, sd, scales, delta, self._codec_ws)
@@ -838,13 +840,10 @@ class RoundEnd:
                     for i in small:
                         result[i] = (hostmem.bytes_from(dh.ctypes.data + 4 * o, 4 * self.numels[i]), [{"int_list": list(self.shapes[i])}])
                         o += self.numels[i]
-            if out is None:
-                out = torch.empty(self.arena_numel, dtype=torch.float32, device=dev)
             if base_arena is not None:
                 if self.plan is not None:
-                    _lib.check_agg(L.ofl_apply_delta_ranges(
-                        base_arena.data_ptr(), delta.data_ptr(), out.data_ptr(), self._rest_n,
-                        self._rest_start.data_ptr(), self._rest_dst.data_ptr(), self._rest_total, _stream(dev)))
+                    _lib.check_agg(L.ofl_apply_delta_ranges(base_arena.data_ptr(), delta.data_ptr(), out.data_ptr(),
+                                                            *self._rest.args, _stream(dev)))
                 else:
                     _lib.check_agg(L.ofl_apply_delta(base_arena.data_ptr(), delta.data_ptr(), self.arena_numel,
                                                      out.data_ptr(), _stream(dev)))
@@ -852,4 +851,4 @@ class RoundEnd:
                 out.copy_(delta)
             if self._gap_idx is not None:
                 out.index_fill_(0, self._gap_idx, 0.0)
-        return out, result, (seeds if payloads else self._seeds[:len(self.numels)])
+        return out, result, (seeds if payloads else self._seeds[:T])

@@ -25,6 +25,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 
 #include "median_net.h"
@@ -33,7 +34,120 @@
 namespace agg {
 
 constexpr int kNT = 256;
-constexpr int kMaxC = 16;  // collaborators per launch (more: chained through agg_out)
+constexpr int kMaxC = 16;  // collaborators per launch (more: chained through agg)
+
+// ---- what the kernels below share ---------------------------------------------
+
+// s + term(c0) + ... + term(n - 1), left to right and rounded after every
+// operation: the sequence NumPy performs over the collaborator axis
+template <class F>
+__device__ __forceinline__ double add_in_order(double s, int c0, int n, F term) {
+#pragma clang fp contract(off)
+    for (int c = c0; c < n; ++c) s = s + term(c);
+    return s;
+}
+
+// NumPy's pairwise sum of p(c0) .. p(c0 + n - 1), the order in which it
+// reduces a 1-D array (numpy/_core/src/umath/loops_utils.h.src: < 8 terms
+// summed from +0.0; up to 128 with eight accumulators combined
+// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) then the tail; larger blocks split in
+// halves rounded down to a multiple of 8).  np_pairwise_block is the part
+// for n <= 128, which does not recurse.
+template <class F>
+__device__ __forceinline__ double np_pairwise_block(F p, int c0, int n) {
+#pragma clang fp contract(off)
+    if (n < 8) {
+        double r = 0.0;
+        for (int k = 0; k < n; ++k) r = r + p(c0 + k);
+        return r;
+    }
+    double r[8];
+    for (int k = 0; k < 8; ++k) r[k] = p(c0 + k);
+    int k = 8;
+    for (; k < n - (n % 8); k += 8)
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + p(c0 + k + j);
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; k < n; ++k) res = res + p(c0 + k);
+    return res;
+}
+template <class F>
+__device__ double np_pairwise(F p, int c0, int n) {
+#pragma clang fp contract(off)
+    if (n <= 128) return np_pairwise_block(p, c0, n);
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    return np_pairwise(p, c0, n2) + np_pairwise(p, c0 + n2, n - n2);
+}
+
+// where an average goes: the aggregate and generate_delta's outputs
+struct DeltaOut {
+    const float* base;  // nullable: delta = average when absent
+    double* agg;        // nullable unless chained: running float64 sums / average
+    double* delta64;    // nullable
+    float* delta32;     // nullable
+    __device__ __forceinline__ double delta(int64_t i, double avg) const {
+#pragma clang fp contract(off)
+        return base ? avg - (double)base[i] : avg;
+    }
+    __device__ __forceinline__ void put(int64_t i, double avg) const {
+        const double d = delta(i, avg);
+        if (agg) agg[i] = avg;
+        if (delta64) delta64[i] = d;
+        if (delta32) delta32[i] = (float)d;
+    }
+};
+
+// listed element ranges of an arena, packed back to back
+struct Ranges {
+    const int64_t* start;  // device [nr]
+    const int64_t* dst;    // device [nr + 1] exclusive prefix of the counts
+    int nr;
+    __device__ __forceinline__ int64_t total() const { return dst[nr]; }
+    // packed index j -> its range; i: the arena element
+    __device__ __forceinline__ int find(int64_t j, int64_t& i) const {
+        int lo = 0, hi = nr - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (dst[mid] <= j) lo = mid; else hi = mid - 1;
+        }
+        i = start[lo] + (j - dst[lo]);
+        return lo;
+    }
+};
+
+// s + v[0] + v[STRIDE] + ... (m values staged in LDS), left to right: the
+// dependent add chain that one lane runs, loads issued eight ahead of the adds
+template <typename T, int STRIDE>
+__device__ __forceinline__ T lds_chain(T s, const T* v, int m) {
+#pragma clang fp contract(off)
+    int k = 0;
+    for (; k + 8 <= m; k += 8) {
+        T t[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t[q] = v[(k + q) * STRIDE];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) s = s + t[q];
+    }
+    for (; k < m; ++k) s = s + v[k * STRIDE];
+    return s;
+}
+
+// an elementwise kernel's body: quad(i) on 4 consecutive elements per thread
+// while the arenas are 16-B aligned (vec), elem(i) on the tail; grid-stride
+template <class Q, class E>
+__device__ __forceinline__ void quads_then_tail(int64_t n, int vec, Q quad, E elem) {
+    const int64_t stride = (int64_t)gridDim.x * kNT;
+    const int64_t t0 = (int64_t)blockIdx.x * kNT + threadIdx.x;
+    int64_t tail = 0;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        for (int64_t q = t0; q < n4; q += stride) quad(4 * q);
+        tail = 4 * n4;
+    }
+    for (int64_t i = tail + t0; i < n; i += stride) elem(i);
+}
+
+// ---- WeightedAverage ------------------------------------------------------------
 
 struct WavgArgs {
     const float* x[kMaxC];
@@ -41,36 +155,23 @@ struct WavgArgs {
     int nc;            // collaborators in this launch
     int first, last;   // first launch starts from the first product; last divides
     double wsum;       // float64 sum of all weights (NumPy's)
-    const float* base; // nullable: delta = average when absent
-    double* acc;       // nullable unless chained: running float64 sums / average
-    double* delta64;   // nullable
-    float* delta32;    // nullable
+    DeltaOut o;
     int64_t n;
 };
 
 // running sum over this launch's collaborators, continuing from s0 (first
-// launch: from the first product) -- the sequence NumPy performs, rounded
-// after every operation
+// launch: from the first product)
 __device__ __forceinline__ double wavg_sum(const WavgArgs& a, int64_t i, double s0) {
 #pragma clang fp contract(off)
-    double s = a.first ? (double)a.x[0][i] * a.w[0] : s0;
-    for (int c = a.first ? 1 : 0; c < a.nc; ++c) s = s + (double)a.x[c][i] * a.w[c];
-    return s;
-}
-__device__ __forceinline__ double wavg_delta(const WavgArgs& a, int64_t i, double s, double& avg) {
-#pragma clang fp contract(off)
-    avg = s / a.wsum;
-    return a.base ? avg - (double)a.base[i] : avg;
+    auto term = [&](int c) { return (double)a.x[c][i] * a.w[c]; };
+    return add_in_order(a.first ? term(0) : s0, a.first ? 1 : 0, a.nc, term);
 }
 
 __device__ __forceinline__ void wavg_elem(const WavgArgs& a, int64_t i) {
-    const double s = wavg_sum(a, i, a.first ? 0.0 : a.acc[i]);
-    if (!a.last) { a.acc[i] = s; return; }
-    double avg;
-    const double d = wavg_delta(a, i, s, avg);
-    if (a.acc) a.acc[i] = avg;
-    if (a.delta64) a.delta64[i] = d;
-    if (a.delta32) a.delta32[i] = (float)d;
+#pragma clang fp contract(off)
+    const double s = wavg_sum(a, i, a.first ? 0.0 : a.o.agg[i]);
+    if (!a.last) { a.o.agg[i] = s; return; }
+    a.o.put(i, s / a.wsum);
 }
 
 // 4 consecutive elements per thread: 16-B loads of every collaborator's
@@ -83,7 +184,7 @@ __device__ __forceinline__ void wavg_quad(const WavgArgs& a, int64_t i) {
         s[0] = (double)v.x * a.w[0]; s[1] = (double)v.y * a.w[0];
         s[2] = (double)v.z * a.w[0]; s[3] = (double)v.w * a.w[0];
     } else {
-        for (int k = 0; k < 4; ++k) s[k] = a.acc[i + k];
+        for (int k = 0; k < 4; ++k) s[k] = a.o.agg[i + k];
     }
     for (int c = a.first ? 1 : 0; c < a.nc; ++c) {
         const float4 v = *reinterpret_cast<const float4*>(a.x[c] + i);
@@ -92,84 +193,47 @@ __device__ __forceinline__ void wavg_quad(const WavgArgs& a, int64_t i) {
         s[2] = s[2] + (double)v.z * w; s[3] = s[3] + (double)v.w * w;
     }
     if (!a.last) {
-        for (int k = 0; k < 4; ++k) a.acc[i + k] = s[k];
+        for (int k = 0; k < 4; ++k) a.o.agg[i + k] = s[k];
         return;
     }
     float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.base) b = *reinterpret_cast<const float4*>(a.base + i);
+    if (a.o.base) b = *reinterpret_cast<const float4*>(a.o.base + i);
     const float bb[4] = {b.x, b.y, b.z, b.w};
     double d[4];
     for (int k = 0; k < 4; ++k) {
         const double avg = s[k] / a.wsum;
-        if (a.acc) a.acc[i + k] = avg;
-        d[k] = a.base ? avg - (double)bb[k] : avg;
+        if (a.o.agg) a.o.agg[i + k] = avg;
+        d[k] = a.o.base ? avg - (double)bb[k] : avg;
     }
-    if (a.delta64)
-        for (int k = 0; k < 4; ++k) a.delta64[i + k] = d[k];
-    if (a.delta32) *reinterpret_cast<float4*>(a.delta32 + i) = make_float4((float)d[0], (float)d[1], (float)d[2], (float)d[3]);
+    if (a.o.delta64)
+        for (int k = 0; k < 4; ++k) a.o.delta64[i + k] = d[k];
+    if (a.o.delta32) *reinterpret_cast<float4*>(a.o.delta32 + i) = make_float4((float)d[0], (float)d[1], (float)d[2], (float)d[3]);
 }
 
 __global__ __launch_bounds__(kNT) void k_wavg_delta(WavgArgs a, int vec) {
-    const int64_t stride = (int64_t)gridDim.x * kNT;
-    const int64_t t0 = (int64_t)blockIdx.x * kNT + threadIdx.x;
-    int64_t tail = 0;
-    if (vec) {
-        const int64_t n4 = a.n >> 2;
-        for (int64_t q = t0; q < n4; q += stride) wavg_quad(a, 4 * q);
-        tail = 4 * n4;
-    }
-    for (int64_t i = tail + t0; i < a.n; i += stride) wavg_elem(a, i);
+    quads_then_tail(a.n, vec, [&](int64_t i) { wavg_quad(a, i); }, [&](int64_t i) { wavg_elem(a, i); });
 }
 
 // Single-element tensors: NumPy reduces a (C, 1) stack as a 1-D array, i.e.
-// pairwise_sum of all C products (numpy/_core/src/umath/loops_utils.h.src:
-// < 8 terms summed from +0.0; up to 128 with eight
-// accumulators combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) then the tail;
-// larger blocks split in halves rounded down to a multiple of 8).
+// np_pairwise of all C products.
 struct PointArgs {
     const float* const* x;  // device [nc]
     const double* w;        // device [nc]
     int nc;
     double wsum;
-    const float* base;
+    DeltaOut o;
     const int64_t* idx;     // device [np]
     int np;
-    double* acc;
-    double* delta64;
-    float* delta32;
 };
-__device__ double np_pairwise(const PointArgs& a, int64_t i, int c0, int n) {
+__device__ __forceinline__ auto point_term(const PointArgs& a, int64_t i) {
 #pragma clang fp contract(off)
-    auto p = [&](int c) { return (double)a.x[c][i] * a.w[c]; };
-    if (n < 8) {
-        double r = 0.0;
-        for (int k = 0; k < n; ++k) r = r + p(c0 + k);
-        return r;
-    }
-    if (n <= 128) {
-        double r[8];
-        for (int k = 0; k < 8; ++k) r[k] = p(c0 + k);
-        int k = 8;
-        for (; k < n - (n % 8); k += 8)
-            for (int j = 0; j < 8; ++j) r[j] = r[j] + p(c0 + k + j);
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; k < n; ++k) res = res + p(c0 + k);
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise(a, i, c0, n2) + np_pairwise(a, i, c0 + n2, n - n2);
+    return [&a, i](int c) { return (double)a.x[c][i] * a.w[c]; };
 }
 __global__ __launch_bounds__(64) void k_wavg_points(PointArgs a) {
 #pragma clang fp contract(off)
     for (int j = blockIdx.x * 64 + threadIdx.x; j < a.np; j += gridDim.x * 64) {
         const int64_t i = a.idx[j];
-        const double s = np_pairwise(a, i, 0, a.nc);
-        const double avg = s / a.wsum;
-        if (a.acc) a.acc[i] = avg;
-        const double d = a.base ? avg - (double)a.base[i] : avg;
-        if (a.delta64) a.delta64[i] = d;
-        if (a.delta32) a.delta32[i] = (float)d;
+        a.o.put(i, np_pairwise(point_term(a, i), 0, a.nc) / a.wsum);
     }
 }
 
@@ -178,60 +242,40 @@ __global__ __launch_bounds__(64) void k_wavg_points(PointArgs a) {
 // tensors use the pairwise order)
 struct RangeArgs {
     PointArgs p;
-    const int64_t* start;   // device [nr]
-    const int64_t* dst;     // device [nr + 1] exclusive prefix of the counts
-    const int32_t* single;  // device [nr]
-    int nr;
+    Ranges rg;
+    const int32_t* single;  // device [rg.nr]
 };
 __global__ __launch_bounds__(kNT) void k_wavg_ranges(RangeArgs r, double* out) {
 #pragma clang fp contract(off)
-    const int64_t total = r.dst[r.nr];
+    const int64_t total = r.rg.total();
     for (int64_t j = (int64_t)blockIdx.x * kNT + threadIdx.x; j < total; j += (int64_t)gridDim.x * kNT) {
-        int lo = 0, hi = r.nr - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (r.dst[mid] <= j) lo = mid; else hi = mid - 1;
-        }
-        const int64_t i = r.start[lo] + (j - r.dst[lo]);
-        double s;
-        if (r.single[lo]) {
-            s = np_pairwise(r.p, i, 0, r.p.nc);
-        } else {
-            s = (double)r.p.x[0][i] * r.p.w[0];
-            for (int c = 1; c < r.p.nc; ++c) s = s + (double)r.p.x[c][i] * r.p.w[c];
-        }
-        const double avg = s / r.p.wsum;
-        out[j] = r.p.base ? avg - (double)r.p.base[i] : avg;
+        int64_t i;
+        const int t = r.rg.find(j, i);
+        const auto term = point_term(r.p, i);
+        const double s = r.single[t] ? np_pairwise(term, 0, r.p.nc) : add_in_order(term(0), 1, r.p.nc, term);
+        out[j] = r.p.o.delta(i, s / r.p.wsum);
     }
 }
 
-// serial float64 sum of each packed range, left to right like Python's sum()
-// over NumPy scalars: one 256-thread block per range stages 2048 values at a
-// time in LDS, then one lane runs the dependent add chain from LDS (loads
-// issued eight ahead of the adds)
-__global__ __launch_bounds__(256) void k_range_sums(const double* packed, const int64_t* dst, double* sums) {
-    __shared__ double v[2048];
+// serial sum of each packed range, left to right like Python's sum() over
+// NumPy scalars: one 256-thread block per range stages 2048 values at a
+// time in LDS, then one lane runs the dependent add chain from LDS
+// (lds_chain).  For float32 values the chain is a float32 add per element
+// (sum() over np.float32 scalars); the sum is stored widened
+template <typename T>
+__global__ __launch_bounds__(256) void k_range_sums(const T* packed, const int64_t* dst, double* sums) {
+    __shared__ T v[2048];
     const int r = blockIdx.x;
     const int64_t j0 = dst[r], j1 = dst[r + 1];
-    double s = 0.0;
+    T s = 0;
     for (int64_t c0 = j0; c0 < j1; c0 += 2048) {
         const int m = (int)(j1 - c0 < 2048 ? j1 - c0 : 2048);
         __syncthreads();
         for (int k = threadIdx.x; k < m; k += 256) v[k] = packed[c0 + k];
         __syncthreads();
-        if (threadIdx.x == 0) {
-            int k = 0;
-            for (; k + 8 <= m; k += 8) {
-                double t[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) t[q] = v[k + q];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) s = s + t[q];
-            }
-            for (; k < m; ++k) s = s + v[k];
-        }
+        if (threadIdx.x == 0) s = lds_chain<T, 1>(s, v, m);
     }
-    if (threadIdx.x == 0) sums[r] = s;
+    if (threadIdx.x == 0) sums[r] = (double)s;
 }
 
 // CPython's hash of a finite float (Objects/object.c _Py_HashDouble, modulus
@@ -262,14 +306,19 @@ __device__ int64_t py_hash_double(double v) {
     if (x == ~0ull) x = ~0ull - 1ull;
     return (int64_t)x;
 }
-// the Eden seed of each tensor from its serial float64 sum and its np.random
-// draw (eden_pipeline.py:771-772): (hash(sum * 13 + 7) + draw) % 2^16
+// the Eden seed of each tensor from its serial sum and its np.random draw
+// (eden_pipeline.py:771-772): (hash(sum * 13 + 7) + draw) % 2^16.  T is the
+// type the sum was formed in: NumPy >= 2 scalar promotion keeps
+// np.float32(sum) * 13 + 7 in float32 (two roundings); hash() of a np.float32
+// is the hash of its value as a Python float
+template <typename T>
 __global__ __launch_bounds__(64) void k_seeds(const double* sums, const int64_t* draws, int n, uint32_t* seeds) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    const double t = sums[i] * 13.0 + 7.0;
-    const int64_t h = py_hash_double(t) + draws[i];
+    T t = (T)sums[i] * (T)13;
+    t = t + (T)7;
+    const int64_t h = py_hash_double((double)t) + draws[i];
     seeds[i] = (uint32_t)(((h % 65536) + 65536) % 65536);
 }
 
@@ -297,16 +346,11 @@ __global__ __launch_bounds__(kNT) void k_unshift64(const float* data, const doub
 
 // apply_delta on listed ranges (device tables): the tensors the codec does
 // not touch when the decode itself adds the base (ofl_eden_decode_add)
-__global__ __launch_bounds__(kNT) void k_apply_ranges(const float* base, const float* delta, float* out,
-                                                      const int64_t* start, const int64_t* dst, int nr) {
-    const int64_t total = dst[nr];
+__global__ __launch_bounds__(kNT) void k_apply_ranges(const float* base, const float* delta, float* out, Ranges rg) {
+    const int64_t total = rg.total();
     for (int64_t j = (int64_t)blockIdx.x * kNT + threadIdx.x; j < total; j += (int64_t)gridDim.x * kNT) {
-        int lo = 0, hi = nr - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (dst[mid] <= j) lo = mid; else hi = mid - 1;
-        }
-        const int64_t i = start[lo] + (j - dst[lo]);
+        int64_t i;
+        rg.find(j, i);
         out[i] = base[i] + delta[i];
     }
 }
@@ -315,18 +359,13 @@ __global__ __launch_bounds__(kNT) void k_apply_ranges(const float* base, const f
 // elements the fused round-end encode does not compute itself
 // (ofl_eden_encode_wavg: slices of <= 2^15 elements and the tensors the codec
 // does not touch)
-__global__ __launch_bounds__(kNT) void k_wavg_delta32_ranges(WavgArgs a, const int64_t* start, const int64_t* dst,
-                                                             int nr) {
-    const int64_t total = dst[nr];
+__global__ __launch_bounds__(kNT) void k_wavg_delta32_ranges(WavgArgs a, Ranges rg) {
+#pragma clang fp contract(off)
+    const int64_t total = rg.total();
     for (int64_t j = (int64_t)blockIdx.x * kNT + threadIdx.x; j < total; j += (int64_t)gridDim.x * kNT) {
-        int lo = 0, hi = nr - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (dst[mid] <= j) lo = mid; else hi = mid - 1;
-        }
-        const int64_t i = start[lo] + (j - dst[lo]);
-        double avg;
-        a.delta32[i] = (float)wavg_delta(a, i, wavg_sum(a, i, 0.0), avg);
+        int64_t i;
+        rg.find(j, i);
+        a.o.delta32[i] = (float)a.o.delta(i, wavg_sum(a, i, 0.0) / a.wsum);
     }
 }
 
@@ -346,24 +385,51 @@ int afail(int code, const std::string& m) { g_aerr = m; return code; }
         if (e_ != hipSuccess) return afail(OFL_EHIP, std::string(#x " failed: ") + hipGetErrorString(e_)); \
     } while (0)
 
-int grid_for(int64_t n, int per_thread) {
+int cu_count() {
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int64_t want = (n + (int64_t)agg::kNT * per_thread - 1) / ((int64_t)agg::kNT * per_thread);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cus * 16));
+    return cus;
 }
 
-int fill_args(agg::WavgArgs& a, int ncollab, const float* const* xs, const double* weights, double wsum,
-              const float* base, int64_t n) {
-    // shared checks; the per-launch collaborator slots are filled by the caller
-    if (ncollab < 1 || !xs || !weights) return afail(OFL_EINVAL, "wavg: need at least one collaborator");
-    if (n < 0) return afail(OFL_EINVAL, "wavg: negative size");
-    a = agg::WavgArgs{};
-    a.wsum = wsum;
-    a.base = base;
-    a.n = n;
+int grid_for(int64_t n, int per_thread) {
+    const int64_t want = (n + (int64_t)agg::kNT * per_thread - 1) / ((int64_t)agg::kNT * per_thread);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cu_count() * 16));
+}
+
+// an entry point's collaborator table (weights: xs again where it takes
+// none): at least one tensor, none of them null
+int check_collabs(const std::string& who, int ncollab, const float* const* xs, const void* weights) {
+    if (ncollab < 1 || !xs || !weights) return afail(OFL_EINVAL, who + ": need at least one collaborator");
+    for (int c = 0; c < ncollab; ++c)
+        if (!xs[c]) return afail(OFL_EINVAL, who + ": null collaborator tensor");
     return OFL_OK;
+}
+
+// the first nc collaborators' slots of a kernel's argument struct
+template <class A, class W>
+void fill_args(A& a, const float* const* xs, const W* weights, int nc) {
+    for (int c = 0; c < nc; ++c) {
+        a.x[c] = xs[c];
+        a.w[c] = weights[c];
+    }
+}
+
+// 1 where the vector path may run: the nc collaborator tensors and every
+// other arena a kernel touches (null: absent) are 16-B aligned
+template <class... P>
+int aligned16(const float* const* xs, int nc, const P*... arenas) {
+    uintptr_t al = (reinterpret_cast<uintptr_t>(arenas) | ... | uintptr_t{0});
+    for (int c = 0; c < nc; ++c) al |= reinterpret_cast<uintptr_t>(xs[c]);
+    return (al & 15u) ? 0 : 1;
+}
+
+// the seeds of nranges packed ranges: their serial sums, then hash and draw
+template <typename T>
+void launch_sums_seeds(const T* packed, const int64_t* dst, int nranges, const int64_t* draws, uint32_t* seeds,
+                       double* sums, hipStream_t st) {
+    hipLaunchKernelGGL(agg::k_range_sums<T>, dim3(nranges), dim3(256), 0, st, packed, dst, sums);
+    hipLaunchKernelGGL(agg::k_seeds<T>, dim3((nranges + 63) / 64), dim3(64), 0, st, sums, draws, nranges, seeds);
 }
 }  // namespace
 
@@ -373,110 +439,26 @@ const char* ofl_agg_last_error(void) { return g_aerr.c_str(); }
 
 int ofl_wavg_delta(int ncollab, const float* const* xs, const double* weights, double wsum, const float* base,
                    int64_t n, double* agg_out, double* delta64_out, float* delta32_out, void* stream) {
-    agg::WavgArgs a;
-    if (int rc = fill_args(a, ncollab, xs, weights, wsum, base, n)) return rc;
+    if (int rc = check_collabs("wavg", ncollab, xs, weights)) return rc;
+    if (n < 0) return afail(OFL_EINVAL, "wavg: negative size");
     if (ncollab > agg::kMaxC && !agg_out)
         return afail(OFL_EINVAL, "wavg: more than 16 collaborators need agg_out (running sums)");
     if (n == 0) return OFL_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int g = grid_for(n, 4);
+    agg::WavgArgs a{};
+    a.wsum = wsum;
+    a.n = n;
     for (int c0 = 0; c0 < ncollab; c0 += agg::kMaxC) {
         a.nc = std::min(agg::kMaxC, ncollab - c0);
-        for (int c = 0; c < a.nc; ++c) {
-            if (!xs[c0 + c]) return afail(OFL_EINVAL, "wavg: null collaborator tensor");
-            a.x[c] = xs[c0 + c];
-            a.w[c] = weights[c0 + c];
-        }
+        fill_args(a, xs + c0, weights + c0, a.nc);
         a.first = c0 == 0;
         a.last = c0 + a.nc == ncollab;
-        a.acc = agg_out;
-        a.delta64 = a.last ? delta64_out : nullptr;
-        a.delta32 = a.last ? delta32_out : nullptr;
-        uintptr_t al = reinterpret_cast<uintptr_t>(a.base) | reinterpret_cast<uintptr_t>(a.delta32) |
-                       reinterpret_cast<uintptr_t>(a.acc) | reinterpret_cast<uintptr_t>(a.delta64);
-        for (int c = 0; c < a.nc; ++c) al |= reinterpret_cast<uintptr_t>(a.x[c]);
-        hipLaunchKernelGGL(agg::k_wavg_delta, dim3(g), dim3(agg::kNT), 0, st, a, (al & 15u) ? 0 : 1);
+        a.o = {base, agg_out, a.last ? delta64_out : nullptr, a.last ? delta32_out : nullptr};
+        const int vec = aligned16(a.x, a.nc, a.o.base, a.o.delta32, a.o.agg, a.o.delta64);
+        hipLaunchKernelGGL(agg::k_wavg_delta, dim3(g), dim3(agg::kNT), 0, st, a, vec);
         AHIP(hipGetLastError());
     }
-    return OFL_OK;
-}
-
-size_t ofl_wavg_ranges_workspace_bytes(int ncollab, int nranges) {
-    return 16 * (size_t)std::max(ncollab, 1) + 20 * (size_t)(std::max(nranges, 1) + 1) + 512;
-}
-
-int ofl_wavg_delta_ranges(int ncollab, const float* const* xs, const double* weights, double wsum,
-                          const float* base, int nranges, const int64_t* starts, const int64_t* counts,
-                          const int32_t* single, double* out, void* ws, size_t ws_bytes, void* stream) {
-    if (ncollab < 1 || ncollab > 2048 || !xs || !weights)
-        return afail(OFL_EINVAL, "wavg ranges: 1 <= collaborators <= 2048");
-    if (nranges < 1) return OFL_OK;
-    if (!starts || !counts || !ws || ws_bytes < ofl_wavg_ranges_workspace_bytes(ncollab, nranges))
-        return afail(OFL_ESPACE, "wavg ranges: workspace too small");
-    const size_t o_w = 8 * (size_t)ncollab, o_s = 16 * (size_t)ncollab;
-    const size_t o_d = o_s + 8 * (size_t)nranges, o_f = o_d + 8 * (size_t)(nranges + 1);
-    std::string host(o_f + 4 * (size_t)nranges, '\0');
-    memcpy(host.data(), xs, 8 * (size_t)ncollab);
-    memcpy(host.data() + o_w, weights, 8 * (size_t)ncollab);
-    int64_t* hs = reinterpret_cast<int64_t*>(host.data() + o_s);
-    int64_t* hd = reinterpret_cast<int64_t*>(host.data() + o_d);
-    int32_t* hf = reinterpret_cast<int32_t*>(host.data() + o_f);
-    int64_t acc = 0;
-    for (int i = 0; i < nranges; ++i) {
-        if (counts[i] < 0 || starts[i] < 0) return afail(OFL_EINVAL, "wavg ranges: negative range");
-        hs[i] = starts[i];
-        hd[i] = acc;
-        hf[i] = single ? single[i] : 0;
-        acc += counts[i];
-    }
-    hd[nranges] = acc;
-    if (acc == 0) return OFL_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(ws);
-    AHIP(hipMemcpyAsync(w, host.data(), host.size(), hipMemcpyHostToDevice, st));
-    agg::RangeArgs r{};
-    r.p.x = reinterpret_cast<const float* const*>(w);
-    r.p.w = reinterpret_cast<const double*>(w + o_w);
-    r.p.nc = ncollab;
-    r.p.wsum = wsum;
-    r.p.base = base;
-    r.start = reinterpret_cast<const int64_t*>(w + o_s);
-    r.dst = reinterpret_cast<const int64_t*>(w + o_d);
-    r.single = reinterpret_cast<const int32_t*>(w + o_f);
-    r.nr = nranges;
-    hipLaunchKernelGGL(agg::k_wavg_ranges, dim3(grid_for(acc, 1)), dim3(agg::kNT), 0, st, r, out);
-    AHIP(hipGetLastError());
-    AHIP(hipStreamSynchronize(st));  // the staging string must outlive the copy
-    return OFL_OK;
-}
-
-size_t ofl_wavg_range_sums_workspace_bytes(int ncollab, int nranges, int64_t total) {
-    return ofl_wavg_ranges_workspace_bytes(ncollab, nranges) + 8 * (size_t)(std::max<int64_t>(total, 1) + nranges) + 512;
-}
-
-int ofl_wavg_delta_range_sums(int ncollab, const float* const* xs, const double* weights, double wsum,
-                              const float* base, int nranges, const int64_t* starts, const int64_t* counts,
-                              const int32_t* single, double* sums, void* ws, size_t ws_bytes, void* stream) {
-    if (nranges < 1) return OFL_OK;
-    if (!sums || !counts) return afail(OFL_EINVAL, "wavg range sums: null output");
-    int64_t total = 0;
-    for (int i = 0; i < nranges; ++i) total += counts[i] > 0 ? counts[i] : 0;
-    if (!ws || ws_bytes < ofl_wavg_range_sums_workspace_bytes(ncollab, nranges, total))
-        return afail(OFL_ESPACE, "wavg range sums: workspace too small");
-    const size_t head = (ofl_wavg_ranges_workspace_bytes(ncollab, nranges) + 255) & ~(size_t)255;
-    char* w = static_cast<char*>(ws);
-    double* packed = reinterpret_cast<double*>(w + head);
-    double* dsums = packed + std::max<int64_t>(total, 1);
-    const int rc = ofl_wavg_delta_ranges(ncollab, xs, weights, wsum, base, nranges, starts, counts, single, packed,
-                                         ws, head, stream);
-    if (rc != OFL_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // the range table the ranges call staged: dst prefix after the pointers, weights and starts
-    const int64_t* dst = reinterpret_cast<const int64_t*>(w + 16 * (size_t)ncollab + 8 * (size_t)nranges);
-    hipLaunchKernelGGL(agg::k_range_sums, dim3(nranges), dim3(256), 0, st, packed, dst, dsums);
-    AHIP(hipGetLastError());
-    AHIP(hipMemcpyAsync(sums, dsums, 8 * (size_t)nranges, hipMemcpyDeviceToHost, st));
-    AHIP(hipStreamSynchronize(st));
     return OFL_OK;
 }
 
@@ -494,14 +476,11 @@ int ofl_wavg_delta_seeds(int ncollab, const float* const* xs_dev, const double* 
     r.p.w = weights_dev;
     r.p.nc = ncollab;
     r.p.wsum = wsum;
-    r.p.base = base;
-    r.start = starts_dev;
-    r.dst = dst_dev;
+    r.p.o.base = base;
+    r.rg = {starts_dev, dst_dev, nranges};
     r.single = single_dev;
-    r.nr = nranges;
     if (total > 0) hipLaunchKernelGGL(agg::k_wavg_ranges, dim3(grid_for(total, 1)), dim3(agg::kNT), 0, st, r, packed_dev);
-    hipLaunchKernelGGL(agg::k_range_sums, dim3(nranges), dim3(256), 0, st, packed_dev, dst_dev, sums_dev);
-    hipLaunchKernelGGL(agg::k_seeds, dim3((nranges + 63) / 64), dim3(64), 0, st, sums_dev, draws_dev, nranges, seeds_dev);
+    launch_sums_seeds<double>(packed_dev, dst_dev, nranges, draws_dev, seeds_dev, sums_dev, st);
     AHIP(hipGetLastError());
     return OFL_OK;
 }
@@ -539,11 +518,8 @@ int ofl_wavg_delta_points(int ncollab, const float* const* xs, const double* wei
     a.idx = reinterpret_cast<const int64_t*>(w + 16 * (size_t)ncollab);
     a.nc = ncollab;
     a.wsum = wsum;
-    a.base = base;
     a.np = npoints;
-    a.acc = agg_out;
-    a.delta64 = delta64_out;
-    a.delta32 = delta32_out;
+    a.o = {base, agg_out, delta64_out, delta32_out};
     hipLaunchKernelGGL(agg::k_wavg_points, dim3((npoints + 63) / 64), dim3(64), 0, st, a);
     AHIP(hipGetLastError());
     AHIP(hipStreamSynchronize(st));  // the staging string must outlive the copy
@@ -574,19 +550,17 @@ int ofl_wavg_delta32_ranges(int ncollab, const float* const* xs, const double* w
     if (nranges < 1 || total <= 0) return OFL_OK;
     if (ncollab > agg::kMaxC) return afail(OFL_EINVAL, "wavg_delta32_ranges: at most 16 collaborators");
     if (!starts || !dst || !delta32_out) return afail(OFL_EINVAL, "wavg_delta32_ranges: bad arguments");
-    agg::WavgArgs a;
-    if (int rc = fill_args(a, ncollab, xs, weights, wsum, base, total)) return rc;
+    if (int rc = check_collabs("wavg", ncollab, xs, weights)) return rc;
+    agg::WavgArgs a{};
+    a.wsum = wsum;
+    a.n = total;
     a.nc = ncollab;
-    for (int c = 0; c < ncollab; ++c) {
-        if (!xs[c]) return afail(OFL_EINVAL, "wavg: null collaborator tensor");
-        a.x[c] = xs[c];
-        a.w[c] = weights[c];
-    }
+    fill_args(a, xs, weights, ncollab);
     a.first = 1;
     a.last = 1;
-    a.delta32 = delta32_out;
+    a.o = {base, nullptr, nullptr, delta32_out};
     hipLaunchKernelGGL(agg::k_wavg_delta32_ranges, dim3(grid_for(total, 1)), dim3(agg::kNT), 0,
-                       static_cast<hipStream_t>(stream), a, starts, dst, nranges);
+                       static_cast<hipStream_t>(stream), a, agg::Ranges{starts, dst, nranges});
     AHIP(hipGetLastError());
     return OFL_OK;
 }
@@ -596,7 +570,7 @@ int ofl_apply_delta_ranges(const float* base, const float* delta, float* out, in
     if (nranges < 1 || total <= 0) return OFL_OK;
     if (!base || !delta || !out || !starts || !dst) return afail(OFL_EINVAL, "apply_delta_ranges: bad arguments");
     hipLaunchKernelGGL(agg::k_apply_ranges, dim3(grid_for(total, 1)), dim3(agg::kNT), 0,
-                       static_cast<hipStream_t>(stream), base, delta, out, starts, dst, nranges);
+                       static_cast<hipStream_t>(stream), base, delta, out, agg::Ranges{starts, dst, nranges});
     AHIP(hipGetLastError());
     return OFL_OK;
 }
@@ -612,24 +586,26 @@ namespace agg {
 constexpr int kMedMaxC = 128;  // the LDS path's column height
 constexpr int kMedLdsNT = 64;  // its block: 128 x 64 floats = 32 KiB of LDS
 
+// a table of N collaborators carries its runtime count only when it is longer
+// than kMaxC: up to kMaxC the kernels are instantiated per count, and the
+// argument structs keep the size they have without the field
+struct NoCount {};
+template <int N>
+using TableCount = std::conditional_t<(N > kMaxC), int, NoCount>;
+
+template <int N>
 struct MedArgs {
-    const float* x[kMaxC];
+    const float* x[N];
     const float* base;  // nullable: delta = median when absent
     float* med;         // nullable
     float* delta;       // nullable: median - base, a float32 subtract
     int64_t n;
+    [[no_unique_address]] TableCount<N> nc;
 };
-struct MedArgsN {
-    const float* x[kMedMaxC];
-    int nc;
-    const float* base;
-    float* med;
-    float* delta;
-    int64_t n;
-};
+static_assert(sizeof(MedArgs<kMaxC>) == 8 * kMaxC + 32);
 
 template <int C>
-__device__ __forceinline__ void med_elem(const MedArgs& a, int64_t i) {
+__device__ __forceinline__ void med_elem(const MedArgs<kMaxC>& a, int64_t i) {
     float v[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) v[c] = a.x[c][i];
@@ -641,7 +617,7 @@ __device__ __forceinline__ void med_elem(const MedArgs& a, int64_t i) {
 // 4 consecutive elements per thread, 16-B loads of every collaborator's arena
 // (the kernel reads 4 C + 4 bytes and writes 4 to 8 per element)
 template <int C>
-__device__ __forceinline__ void med_quad(const MedArgs& a, int64_t i) {
+__device__ __forceinline__ void med_quad(const MedArgs<kMaxC>& a, int64_t i) {
     float4 q[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) q[c] = *reinterpret_cast<const float4*>(a.x[c] + i);
@@ -668,21 +644,13 @@ __device__ __forceinline__ void med_quad(const MedArgs& a, int64_t i) {
 }
 
 template <int C>
-__global__ __launch_bounds__(kNT) void k_median(MedArgs a, int vec) {
-    const int64_t stride = (int64_t)gridDim.x * kNT;
-    const int64_t t0 = (int64_t)blockIdx.x * kNT + threadIdx.x;
-    int64_t tail = 0;
-    if (vec) {
-        const int64_t n4 = a.n >> 2;
-        for (int64_t q = t0; q < n4; q += stride) med_quad<C>(a, 4 * q);
-        tail = 4 * n4;
-    }
-    for (int64_t i = tail + t0; i < a.n; i += stride) med_elem<C>(a, i);
+__global__ __launch_bounds__(kNT) void k_median(MedArgs<kMaxC> a, int vec) {
+    quads_then_tail(a.n, vec, [&](int64_t i) { med_quad<C>(a, i); }, [&](int64_t i) { med_elem<C>(a, i); });
 }
 
 // 17..128 collaborators: every thread insertion-sorts its column in LDS, laid
 // out [c][thread] so the lanes of a wave hit distinct banks
-__global__ __launch_bounds__(kMedLdsNT) void k_median_lds(MedArgsN a) {
+__global__ __launch_bounds__(kMedLdsNT) void k_median_lds(MedArgs<kMedMaxC> a) {
     __shared__ float col[kMedMaxC][kMedLdsNT];
     const int tid = threadIdx.x;
     for (int64_t i = (int64_t)blockIdx.x * kMedLdsNT + tid; i < a.n; i += (int64_t)gridDim.x * kMedLdsNT) {
@@ -724,10 +692,7 @@ struct GmArgs {
     int32_t* iters;   // [nt]
     double* partial;  // [nchunks][16] squared distances of one chunk
     double eps, ftol;
-    const float* base;
-    double* agg;
-    double* delta64;
-    float* delta32;
+    DeltaOut o;
 };
 struct GmW0 {
     double w[kMaxC];
@@ -754,10 +719,7 @@ __device__ __forceinline__ double gm_point(const GmArgs& a, const double (&w)[C]
 #pragma clang fp contract(off)
 #pragma unroll
     for (int c = 0; c < C; ++c) x[c] = a.x[c][i];
-    double s = (double)x[0] * w[0];
-#pragma unroll
-    for (int c = 1; c < C; ++c) s = s + (double)x[c] * w[c];
-    return s / wsum;
+    return add_in_order((double)x[0] * w[0], 1, C, [&](int c) { return (double)x[c] * w[c]; }) / wsum;
 }
 
 // squared distances of every collaborator to the current median, one block per
@@ -798,25 +760,6 @@ __global__ __launch_bounds__(kNT) void k_gm_dist(GmArgs a) {
     }
 }
 
-// NumPy's pairwise sum of n <= 16 values (weights.sum()): in order below 8,
-// eight accumulators combined as a tree from 8 on
-__device__ double np_sum16(const double* v, int n) {
-#pragma clang fp contract(off)
-    if (n < 8) {
-        double r = 0.0;
-        for (int k = 0; k < n; ++k) r = r + v[k];
-        return r;
-    }
-    double r[8];
-    for (int k = 0; k < 8; ++k) r[k] = v[k];
-    int k = 8;
-    for (; k < n - (n % 8); k += 8)
-        for (int j = 0; j < 8; ++j) r[j] = r[j] + v[k + j];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; k < n; ++k) res = res + v[k];
-    return res;
-}
-
 // After distance pass `pass` (0: the first average): add every tensor's chunk
 // partials in chunk order, d_c = sqrt, objective sum_c W_c d_c with the weights
 // the median was formed with, the reference's break test (strict <, so an
@@ -829,8 +772,8 @@ __global__ __launch_bounds__(kNT) void k_gm_update(GmArgs a, int pass, int last)
     const int t = blockIdx.x, lane = threadIdx.x;
     if (a.done[t]) return;
     // the partial rows go through LDS (coalesced loads by the whole block), then
-    // lane c runs collaborator c's add chain from LDS, loads issued eight ahead
-    // of the adds, as k_range_sums does
+    // lane c runs collaborator c's add chain from LDS (lds_chain), as
+    // k_range_sums does
     const int c0 = a.tchunk0[t], c1 = a.tchunk0[t + 1];
     double s = 0.0;
     for (int b = c0; b < c1; b += kStage) {
@@ -838,17 +781,7 @@ __global__ __launch_bounds__(kNT) void k_gm_update(GmArgs a, int pass, int last)
         __syncthreads();
         for (int k = lane; k < m * kMaxC; k += kNT) stage[k] = a.partial[(int64_t)b * kMaxC + k];
         __syncthreads();
-        if (lane < a.nc) {
-            int k = 0;
-            for (; k + 8 <= m; k += 8) {
-                double v[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = stage[(k + q) * kMaxC + lane];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) s = s + v[q];
-            }
-            for (; k < m; ++k) s = s + stage[k * kMaxC + lane];
-        }
+        if (lane < a.nc) s = lds_chain<double, kMaxC>(s, stage + lane, m);
     }
     if (lane < a.nc) d[lane] = sqrt(s);
     __syncthreads();
@@ -867,7 +800,8 @@ __global__ __launch_bounds__(kNT) void k_gm_update(GmArgs a, int pass, int last)
     }
     if (last) return;
     for (int c = 0; c < a.nc; ++c) nw[c] = W[c] / (d[c] > a.eps ? d[c] : a.eps);
-    const double tot = np_sum16(nw, a.nc);
+    // weights.sum() of nc <= 16 values: NumPy's pairwise order
+    const double tot = np_pairwise_block([&](int c) { return nw[c]; }, 0, a.nc);
     double ws = 0.0;
     for (int c = 0; c < a.nc; ++c) {
         const double w = nw[c] / tot;
@@ -891,11 +825,7 @@ __global__ __launch_bounds__(kNT) void k_gm_final(GmArgs a) {
         for (int e = threadIdx.x; e < k.len; e += kNT) {
             const int64_t i = k.start + e;
             float x[C];
-            const double m = gm_point<C>(a, w, wsum, i, x);
-            const double dl = a.base ? m - (double)a.base[i] : m;
-            if (a.agg) a.agg[i] = m;
-            if (a.delta64) a.delta64[i] = dl;
-            if (a.delta32) a.delta32[i] = (float)dl;
+            a.o.put(i, gm_point<C>(a, w, wsum, i, x));
         }
     }
 }
@@ -903,67 +833,21 @@ __global__ __launch_bounds__(kNT) void k_gm_final(GmArgs a) {
 // the delta of an aggregate arena on listed ranges, packed: float64 aggregate
 // -> agg - (double)base; float32 aggregate -> a float32 subtract
 template <typename T>
-__global__ __launch_bounds__(kNT) void k_agg_ranges(const T* agg, const float* base, const int64_t* start,
-                                                    const int64_t* dst, int nr, T* out) {
+__global__ __launch_bounds__(kNT) void k_agg_ranges(const T* agg, const float* base, Ranges rg, T* out) {
 #pragma clang fp contract(off)
-    const int64_t total = dst[nr];
+    const int64_t total = rg.total();
     for (int64_t j = (int64_t)blockIdx.x * kNT + threadIdx.x; j < total; j += (int64_t)gridDim.x * kNT) {
-        int lo = 0, hi = nr - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (dst[mid] <= j) lo = mid; else hi = mid - 1;
-        }
-        const int64_t i = start[lo] + (j - dst[lo]);
+        int64_t i;
+        rg.find(j, i);
         out[j] = base ? agg[i] - (T)base[i] : agg[i];
     }
-}
-
-// k_range_sums for float32 values: the chain is a float32 add per element
-// (sum() over np.float32 scalars); the sum is stored widened
-__global__ __launch_bounds__(256) void k_range_sums32(const float* packed, const int64_t* dst, double* sums) {
-#pragma clang fp contract(off)
-    __shared__ float v[2048];
-    const int r = blockIdx.x;
-    const int64_t j0 = dst[r], j1 = dst[r + 1];
-    float s = 0.0f;
-    for (int64_t c0 = j0; c0 < j1; c0 += 2048) {
-        const int m = (int)(j1 - c0 < 2048 ? j1 - c0 : 2048);
-        __syncthreads();
-        for (int k = threadIdx.x; k < m; k += 256) v[k] = packed[c0 + k];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int k = 0;
-            for (; k + 8 <= m; k += 8) {
-                float t[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) t[q] = v[k + q];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) s = s + t[q];
-            }
-            for (; k < m; ++k) s = s + v[k];
-        }
-    }
-    if (threadIdx.x == 0) sums[r] = (double)s;
-}
-
-// k_seeds for a float32 sum: NumPy >= 2 scalar promotion keeps
-// np.float32(sum) * 13 + 7 in float32 (two roundings); hash() of a np.float32
-// is the hash of its value as a Python float
-__global__ __launch_bounds__(64) void k_seeds32(const double* sums, const int64_t* draws, int n, uint32_t* seeds) {
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    float t = (float)sums[i] * 13.0f;
-    t = t + 7.0f;
-    const int64_t h = py_hash_double((double)t) + draws[i];
-    seeds[i] = (uint32_t)(((h % 65536) + 65536) % 65536);
 }
 
 }  // namespace agg
 
 namespace {
 template <int C>
-void launch_median(const agg::MedArgs& a, int vec, hipStream_t st) {
+void launch_median(const agg::MedArgs<agg::kMaxC>& a, int vec, hipStream_t st) {
     hipLaunchKernelGGL(agg::k_median<C>, dim3(grid_for(a.n, 4)), dim3(agg::kNT), 0, st, a, vec);
 }
 template <int C>
@@ -987,40 +871,35 @@ void launch_gm_final(const agg::GmArgs& a, int grid, hipStream_t st) {
     }
 
 size_t gm_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// ofl_agg_delta_seeds for an aggregate of type T
+template <typename T>
+void launch_agg_seeds(const void* agg, const float* base, agg::Ranges rg, int64_t total, const int64_t* draws,
+                      uint32_t* seeds, double* sums, void* packed_dev, hipStream_t st) {
+    T* packed = static_cast<T*>(packed_dev);
+    if (total > 0)
+        hipLaunchKernelGGL(agg::k_agg_ranges<T>, dim3(grid_for(total, 1)), dim3(agg::kNT), 0, st,
+                           static_cast<const T*>(agg), base, rg, packed);
+    launch_sums_seeds<T>(packed, rg.dst, rg.nr, draws, seeds, sums, st);
+}
 }  // namespace
 
 extern "C" {
 
 int ofl_median_delta(int ncollab, const float* const* xs, const float* base, int64_t n, float* median_out,
                      float* delta_out, void* stream) {
-    if (ncollab < 1 || !xs) return afail(OFL_EINVAL, "median: need at least one collaborator");
+    if (int rc = check_collabs("median", ncollab, xs, xs)) return rc;
     if (ncollab > agg::kMedMaxC) return afail(OFL_EINVAL, "median: at most 128 collaborators");
     if (n < 0) return afail(OFL_EINVAL, "median: negative size");
-    for (int c = 0; c < ncollab; ++c)
-        if (!xs[c]) return afail(OFL_EINVAL, "median: null collaborator tensor");
     if (n == 0 || (!median_out && !delta_out)) return OFL_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (ncollab <= agg::kMaxC) {
-        agg::MedArgs a{};
-        uintptr_t al = reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(median_out) |
-                       reinterpret_cast<uintptr_t>(delta_out);
-        for (int c = 0; c < ncollab; ++c) {
-            a.x[c] = xs[c];
-            al |= reinterpret_cast<uintptr_t>(xs[c]);
-        }
-        a.base = base;
-        a.med = median_out;
-        a.delta = delta_out;
-        a.n = n;
-        OFL_FOR_C16(launch_median, ncollab, a, (al & 15u) ? 0 : 1, st)
+        agg::MedArgs<agg::kMaxC> a{{}, base, median_out, delta_out, n, {}};
+        std::copy(xs, xs + ncollab, a.x);
+        OFL_FOR_C16(launch_median, ncollab, a, aligned16(xs, ncollab, base, median_out, delta_out), st)
     } else {
-        agg::MedArgsN a{};
-        for (int c = 0; c < ncollab; ++c) a.x[c] = xs[c];
-        a.nc = ncollab;
-        a.base = base;
-        a.med = median_out;
-        a.delta = delta_out;
-        a.n = n;
+        agg::MedArgs<agg::kMedMaxC> a{{}, base, median_out, delta_out, n, ncollab};
+        std::copy(xs, xs + ncollab, a.x);
         const int64_t want = (n + agg::kMedLdsNT - 1) / agg::kMedLdsNT;
         const int g = (int)std::min<int64_t>(want, (int64_t)grid_for(n, 1) * 4);
         hipLaunchKernelGGL(agg::k_median_lds, dim3(g), dim3(agg::kMedLdsNT), 0, st, a);
@@ -1038,7 +917,7 @@ int ofl_gmedian_delta(int ncollab, const float* const* xs, const double* w0, int
                       const float* base, int ntensors, const ofl_gm_chunk* chunks_dev, int nchunks,
                       const int32_t* tensor_chunk0_dev, double* agg_out, double* delta64_out, float* delta32_out,
                       int32_t* iters_out, void* ws, size_t ws_bytes, void* stream) {
-    if (ncollab < 1 || !xs || !w0) return afail(OFL_EINVAL, "geometric median: need at least one collaborator");
+    if (int rc = check_collabs("geometric median", ncollab, xs, w0)) return rc;
     if (ncollab > agg::kMaxC) return afail(OFL_EINVAL, "geometric median: at most 16 collaborators");
     if (ntensors < 1 || nchunks < 0 || maxiter < 0) return afail(OFL_EINVAL, "geometric median: bad sizes");
     if (!tensor_chunk0_dev || (nchunks && !chunks_dev)) return afail(OFL_EINVAL, "geometric median: null chunk table");
@@ -1048,11 +927,8 @@ int ofl_gmedian_delta(int ncollab, const float* const* xs, const double* w0, int
     char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
     agg::GmArgs a{};
     agg::GmW0 init{};
-    for (int c = 0; c < ncollab; ++c) {
-        if (!xs[c]) return afail(OFL_EINVAL, "geometric median: null collaborator tensor");
-        a.x[c] = xs[c];
-        init.w[c] = w0[c];
-    }
+    std::copy(xs, xs + ncollab, a.x);
+    std::copy(w0, w0 + ncollab, init.w);
     a.nc = ncollab;
     a.chunks = chunks_dev;
     a.nchunks = nchunks;
@@ -1067,15 +943,9 @@ int ofl_gmedian_delta(int ncollab, const float* const* xs, const double* w0, int
     if (iters_out) a.iters = iters_out;
     a.eps = eps;
     a.ftol = ftol;
-    a.base = base;
-    a.agg = agg_out;
-    a.delta64 = delta64_out;
-    a.delta32 = delta32_out;
+    a.o = {base, agg_out, delta64_out, delta32_out};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int grid = std::max(1, std::min(nchunks, cus * 8));
+    const int grid = std::max(1, std::min(nchunks, cu_count() * 8));
     hipLaunchKernelGGL(agg::k_gm_init, dim3((ntensors + 63) / 64), dim3(64), 0, st, a, init);
     for (int pass = 0; pass <= maxiter; ++pass) {
         if (nchunks) OFL_FOR_C16(launch_gm_dist, ncollab, a, grid, st)
@@ -1093,22 +963,11 @@ int ofl_agg_delta_seeds(const void* agg_dev, int agg_is_f64, const float* base, 
     if (!agg_dev || !starts_dev || !dst_dev || !draws_dev || !seeds_dev || !sums_dev || (total > 0 && !packed_dev))
         return afail(OFL_EINVAL, "agg seeds: null pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int g = grid_for(std::max<int64_t>(total, 1), 1), gs = (nranges + 63) / 64;
-    if (agg_is_f64) {
-        double* packed = static_cast<double*>(packed_dev);
-        if (total > 0)
-            hipLaunchKernelGGL(agg::k_agg_ranges<double>, dim3(g), dim3(agg::kNT), 0, st,
-                               static_cast<const double*>(agg_dev), base, starts_dev, dst_dev, nranges, packed);
-        hipLaunchKernelGGL(agg::k_range_sums, dim3(nranges), dim3(256), 0, st, packed, dst_dev, sums_dev);
-        hipLaunchKernelGGL(agg::k_seeds, dim3(gs), dim3(64), 0, st, sums_dev, draws_dev, nranges, seeds_dev);
-    } else {
-        float* packed = static_cast<float*>(packed_dev);
-        if (total > 0)
-            hipLaunchKernelGGL(agg::k_agg_ranges<float>, dim3(g), dim3(agg::kNT), 0, st,
-                               static_cast<const float*>(agg_dev), base, starts_dev, dst_dev, nranges, packed);
-        hipLaunchKernelGGL(agg::k_range_sums32, dim3(nranges), dim3(256), 0, st, packed, dst_dev, sums_dev);
-        hipLaunchKernelGGL(agg::k_seeds32, dim3(gs), dim3(64), 0, st, sums_dev, draws_dev, nranges, seeds_dev);
-    }
+    const agg::Ranges rg{starts_dev, dst_dev, nranges};
+    if (agg_is_f64)
+        launch_agg_seeds<double>(agg_dev, base, rg, total, draws_dev, seeds_dev, sums_dev, packed_dev, st);
+    else
+        launch_agg_seeds<float>(agg_dev, base, rg, total, draws_dev, seeds_dev, sums_dev, packed_dev, st);
     AHIP(hipGetLastError());
     return OFL_OK;
 }
@@ -1139,7 +998,7 @@ int ofl_agg_delta_seeds(const void* agg_dev, int agg_is_f64, const float* base, 
 
 namespace agg {
 
-constexpr int kAdaMaxC = 128;  // the pointer table's length
+constexpr int kAdaMaxC = 128;  // the long pointer table's length
 
 struct AdaIO {
     const float* base;
@@ -1150,19 +1009,17 @@ struct AdaIO {
     float* delta;  // nullable: p after the step - base, a float32 subtract
     int64_t n;
 };
-struct AdaArgs {  // <= 16 collaborators, unrolled
-    const float* x[kMaxC];
-    float w[kMaxC];
+// N = kMaxC: <= 16 collaborators, unrolled; N = kAdaMaxC: 17..128, a runtime
+// loop over the table
+template <int N>
+struct AdaArgs {
+    const float* x[N];
+    float w[N];
     AdaIO io;
     ofl_adaptive_consts k;
+    [[no_unique_address]] TableCount<N> nc;
 };
-struct AdaArgsN {  // 17..128 collaborators, a runtime loop over the table
-    const float* x[kAdaMaxC];
-    float w[kAdaMaxC];
-    int nc;
-    AdaIO io;
-    ofl_adaptive_consts k;
-};
+static_assert(sizeof(AdaArgs<kMaxC>) == 288);
 
 // np.sign: -1, 0, +1, and the NaN itself for a NaN
 __device__ __forceinline__ float np_signf(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : (d == 0.f ? 0.f : d)); }
@@ -1263,26 +1120,19 @@ __device__ __forceinline__ void ada_quad(const A& a, int64_t i) {
     if (a.io.delta) *reinterpret_cast<float4*>(a.io.delta + i) = make_float4(p.x - b.x, p.y - b.y, p.z - b.z, p.w - b.w);
 }
 
-// C > 0: that many collaborators unrolled from AdaArgs; C == 0: a.nc of AdaArgsN
+// C > 0: that many collaborators unrolled from AdaArgs<kMaxC>; C == 0: a.nc of
+// AdaArgs<kAdaMaxC>
 template <int C, class A>
 __global__ __launch_bounds__(kNT) void k_adaptive(A a, int vec) {
-    const int64_t stride = (int64_t)gridDim.x * kNT;
-    const int64_t t0 = (int64_t)blockIdx.x * kNT + threadIdx.x;
-    int64_t tail = 0;
-    if (vec) {
-        const int64_t n4 = a.io.n >> 2;
-        for (int64_t q = t0; q < n4; q += stride) ada_quad<C>(a, 4 * q);
-        tail = 4 * n4;
-    }
-    for (int64_t i = tail + t0; i < a.io.n; i += stride) ada_elem<C>(a, i);
+    quads_then_tail(a.io.n, vec, [&](int64_t i) { ada_quad<C>(a, i); }, [&](int64_t i) { ada_elem<C>(a, i); });
 }
 
 }  // namespace agg
 
 namespace {
-template <int C>
-void launch_adaptive(const agg::AdaArgs& a, int vec, hipStream_t st) {
-    hipLaunchKernelGGL((agg::k_adaptive<C, agg::AdaArgs>), dim3(grid_for(a.io.n, 4)), dim3(agg::kNT), 0, st, a, vec);
+template <int C, class A>
+void launch_adaptive(const A& a, int vec, hipStream_t st) {
+    hipLaunchKernelGGL((agg::k_adaptive<C, A>), dim3(grid_for(a.io.n, 4)), dim3(agg::kNT), 0, st, a, vec);
 }
 }  // namespace
 
@@ -1291,42 +1141,25 @@ extern "C" {
 int ofl_adaptive_step(int ncollab, const float* const* xs, const float* weights, const float* base, int64_t n,
                       float* p, float* m, float* v, const ofl_adaptive_consts* k, float* agg_out, float* delta_out,
                       void* stream) {
-    if (ncollab < 1 || !xs || !weights) return afail(OFL_EINVAL, "adaptive step: need at least one collaborator");
+    if (int rc = check_collabs("adaptive step", ncollab, xs, weights)) return rc;
     if (ncollab > agg::kAdaMaxC) return afail(OFL_EINVAL, "adaptive step: at most 128 collaborators");
     if (n < 0) return afail(OFL_EINVAL, "adaptive step: negative size");
     if (!k || k->kind < OFL_ADAPTIVE_ADAM || k->kind > OFL_ADAPTIVE_ADAGRAD)
         return afail(OFL_EINVAL, "adaptive step: kind must be OFL_ADAPTIVE_ADAM, _YOGI or _ADAGRAD");
-    for (int c = 0; c < ncollab; ++c)
-        if (!xs[c]) return afail(OFL_EINVAL, "adaptive step: null collaborator tensor");
     if (n == 0) return OFL_OK;
     if (!base || !p || !v || (k->kind != OFL_ADAPTIVE_ADAGRAD && !m))
         return afail(OFL_EINVAL, "adaptive step: base and the state arenas are required");
-    agg::AdaIO io{base, p, k->kind != OFL_ADAPTIVE_ADAGRAD ? m : nullptr, v, agg_out, delta_out, n};
-    uintptr_t al = reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(io.m) |
-                   reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(agg_out) |
-                   reinterpret_cast<uintptr_t>(delta_out);
-    for (int c = 0; c < ncollab; ++c) al |= reinterpret_cast<uintptr_t>(xs[c]);
-    const int vec = (al & 15u) ? 0 : 1;
+    const agg::AdaIO io{base, p, k->kind != OFL_ADAPTIVE_ADAGRAD ? m : nullptr, v, agg_out, delta_out, n};
+    const int vec = aligned16(xs, ncollab, base, p, io.m, v, agg_out, delta_out);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (ncollab <= agg::kMaxC) {
-        agg::AdaArgs a{};
-        for (int c = 0; c < ncollab; ++c) {
-            a.x[c] = xs[c];
-            a.w[c] = weights[c];
-        }
-        a.io = io;
-        a.k = *k;
+        agg::AdaArgs<agg::kMaxC> a{{}, {}, io, *k, {}};
+        fill_args(a, xs, weights, ncollab);
         OFL_FOR_C16(launch_adaptive, ncollab, a, vec, st)
     } else {
-        agg::AdaArgsN a{};
-        for (int c = 0; c < ncollab; ++c) {
-            a.x[c] = xs[c];
-            a.w[c] = weights[c];
-        }
-        a.nc = ncollab;
-        a.io = io;
-        a.k = *k;
-        hipLaunchKernelGGL((agg::k_adaptive<0, agg::AdaArgsN>), dim3(grid_for(n, 4)), dim3(agg::kNT), 0, st, a, vec);
+        agg::AdaArgs<agg::kAdaMaxC> a{{}, {}, io, *k, ncollab};
+        fill_args(a, xs, weights, ncollab);
+        launch_adaptive<0>(a, vec, st);
     }
     AHIP(hipGetLastError());
     return OFL_OK;
