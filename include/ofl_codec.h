@@ -317,6 +317,35 @@ int ofl_kmeans1d_batch_tab(int ntensors, const float* x_arena, const int64_t* of
                            int n_init, uint64_t seed, int max_exact, int value_f64, float* ranks_out,
                            ofl_label_rec* label_tab, double* centres, int64_t* counts, double* inertia,
                            int32_t* nuniq, double* uniq, void* ws, size_t ws_bytes, void* stream);
+/* ofl_kmeans1d_batch_tab with one seed per tensor (seeds: host, [ntensors]):
+ * tensor t runs exactly as a one-tensor call of ofl_kmeans1d_batch_tab with
+ * seed = seeds[t] -- the same restart streams (the tensor index mixed into
+ * them is 0), and nothing else depends on what the batch holds (blocks,
+ * histograms and reductions are per tensor; integer atomics) -- so centres,
+ * counts, inertia, uniq, ranks and label records are equal bit for bit.
+ * value_tab (DEVICE, ntensors records laid out like ofl_label_rec, may be NULL;
+ * k <= 8 and ascending ranges as for label_tab): the last eight floats hold,
+ * for cluster j, the float32 value the reference's backward gives that
+ * cluster's elements: v = rank[j]; for i = 0 .. nuniq - 1 in order: if v ==
+ * (float)i then v = (float)uniq[i] (kc_pipeline.py:79-83; a value equal to a
+ * later key is replaced again).  ofl_label_apply reads these records. */
+int ofl_kmeans1d_batch_seeds(int ntensors, const float* x_arena, const int64_t* offsets, const int64_t* numels, int k,
+                             int n_init, const uint64_t* seeds, int max_exact, int value_f64, float* ranks_out,
+                             ofl_label_rec* label_tab, ofl_label_rec* value_tab, double* centres, int64_t* counts,
+                             double* inertia, int32_t* nuniq, double* uniq, void* ws, size_t ws_bytes, void* stream);
+/* The round end's tail in one pass: for every element i of every record's
+ * [start, end): out[i] = base[i] + rank[j] (float32 add; rank[j] itself if
+ * base is NULL), j the first cluster with x_arena[i] <= mid[j] (the > chain of
+ * the k-means labelling: a NaN takes cluster 0) -- decompress(compress(delta))
+ * of a lossy pipeline followed by apply_delta, without a rank array or a
+ * decoded delta.  recs: DEVICE, ntensors records (value records of
+ * ofl_kmeans1d_batch_seeds, or built by the caller, e.g. the ternary rule:
+ * mid = {largest negative denormal, 0, +inf ...}), ascending and
+ * non-overlapping.  out may alias base or x_arena; elements outside every
+ * record are not written.  Async; null x_arena / recs / out or ntensors < 1:
+ * OFL_EINVAL before any HIP call. */
+int ofl_label_apply(const float* x_arena, const ofl_label_rec* recs, int ntensors, const float* base, float* out,
+                    void* stream);
 int ofl_kmeans1d_label(const float* x, int64_t n, const double* centres, int k,
                        const float* rank_of_cluster, float* out, void* stream);
 int ofl_sparsify_topk(const float* x, int64_t n, int64_t k, float* sparse_out, float* kept_min,

@@ -26,7 +26,7 @@ EXPORTS = (
     "ofl_eden_plan_launch_info", "ofl_eden_plan_launch_detail", "ofl_eden_plan_profile_collect", "ofl_serial_sum_f32", "ofl_serial_sum_f32_mt", "ofl_serial_sum_copy_f32",
     "ofl_serial_sum_f64", "ofl_host_copy_many", "ofl_serial_sums_many", "ofl_lossy_last_error", "ofl_lossy_workspace_bytes", "ofl_kmeans1d_fit",
     "ofl_kmeans1d_batch_workspace_bytes", "ofl_kmeans1d_batch", "ofl_kmeans1d_batch_tab",
-    "ofl_kmeans1d_label", "ofl_sparsify_topk", "ofl_ternary_stats", "ofl_ternary_ranks", "ofl_lut_decode",
+    "ofl_kmeans1d_batch_seeds", "ofl_label_apply", "ofl_kmeans1d_label", "ofl_sparsify_topk", "ofl_ternary_stats", "ofl_ternary_ranks", "ofl_lut_decode",
     "ofl_lut_decode_batch_workspace_bytes", "ofl_lut_decode_batch",
     "ofl_sparsify_topk_batch_workspace_bytes", "ofl_sparsify_topk_batch",
     "ofl_ternary_ranks_batch_workspace_bytes", "ofl_ternary_ranks_batch",
@@ -128,6 +128,11 @@ def _bind(L):
     L.ofl_kmeans1d_batch_tab.argtypes = [i32, vp, vp, vp, i32, i32, ctypes.c_uint64, i32, i32, vp, vp, vp, vp, vp, vp,
                                          vp, vp, sz, vp]
     L.ofl_kmeans1d_batch_tab.restype = i32
+    L.ofl_kmeans1d_batch_seeds.argtypes = [i32, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                           sz, vp]
+    L.ofl_kmeans1d_batch_seeds.restype = i32
+    L.ofl_label_apply.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.ofl_label_apply.restype = i32
     L.ofl_kmeans1d_label.argtypes = [vp, i64, vp, i32, vp, vp, vp]
     L.ofl_kmeans1d_label.restype = i32
     L.ofl_sparsify_topk.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]

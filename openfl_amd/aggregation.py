@@ -24,6 +24,11 @@ the reference's functions tensor by tensor with an openfl_amd EdenPipeline
 (tests/test_gpu_aggregation.py).  No CPU fallback: without the library or a
 GPU every call raises CodecError.
 
+RoundEnd takes a KCPipeline, SKCPipeline or STCPipeline too: the same
+aggregation kernels, then _LossyTail instead of the Eden seeds, encode and
+decode (batched k-means with one np.random seed per tensor, one labelling +
+decode + apply pass; DESIGN.md 3.9, tests/test_gpu_lossy_round_end.py).
+
 Beside the weighted average: Median and GeometricMedian, and the FedOpt
 server optimisers AdamAdaptiveAggregation, YogiAdaptiveAggregation and
 AdagradAdaptiveAggregation (core/adaptive_aggregation.py on
@@ -36,9 +41,12 @@ import ctypes
 import numpy as np
 import torch
 
-from openfl_amd import _lib, hostmem
+from openfl_amd import _lib, hostmem, lossy
 from openfl_amd.codec import EdenPlan, resolve_device, slice_plan
 from openfl_amd.pipelines.eden_pipeline import _FAST_SEED_PREFIX
+from openfl_amd.pipelines.kc_pipeline import KCPipeline
+from openfl_amd.pipelines.skc_pipeline import SKCPipeline
+from openfl_amd.pipelines.stc_pipeline import STCPipeline, _topk_count, ternary_map
 
 _ALIGN = 64
 _ROW_TILE = 1 << 15  # slices above this go through the row passes (kRowLog)
@@ -502,11 +510,140 @@ _WavgSeeds = collections.namedtuple("_WavgSeeds", "w64 wsum fused")
 _AggSeeds = collections.namedtuple("_AggSeeds", "agg is_f64 base")
 
 
+class _LossyTail:
+    """What follows the delta when the pipeline is a KCPipeline, SKCPipeline or
+    STCPipeline: compress, decompress and apply_delta of every tensor.  The
+    bytes are decoded straight after they are encoded and gzip is lossless, so
+    decompress(compress(delta)) is the delta's labelling rule followed by the
+    reference's key -> value replacement (kc_pipeline.py:79-83), and the new
+    model is base + value_of(label(delta)) per element: one lossy.label_apply
+    over value records, no rank array and no decoded delta (the ranks are
+    written only where payloads are asked for).
+      KC   k-means of the delta arena, one np.random seed per tensor
+      SKC  top-k into a sparse arena, k-means of that (float64 centres)
+      STC  top-k, the ternary rule as a record built from its statistics
+    Tensors the device path does not take (n < n_clusters for KC / SKC, empty
+    ones) go through the pipeline's own forward / backward on the host, with
+    their delta in the dtype the reference computes it in."""
+
+    def __init__(self, re, pipeline):
+        self.re, self.pipeline = re, pipeline
+        self.kind = "kc" if isinstance(pipeline, KCPipeline) else "skc" if isinstance(pipeline, SKCPipeline) else "stc"
+        trs = pipeline.transformers
+        self.gz = trs[-1]
+        self.k = 0
+        if self.kind != "stc":
+            self.k = int(trs[-2].n_cluster)
+            if not 1 <= self.k <= 8:
+                raise _lib.CodecError(f"RoundEnd: n_clusters = {self.k}; label records need 1 <= k <= 8")
+        # the reference clusters the delta in its own dtype; SKC's sparsifier emits float64
+        self.value_f64 = self.kind == "skc" or re.aggregation in ("weighted_average", "geometric_median")
+        take = (lambda n: n > 0) if self.kind == "stc" else (lambda n: n >= self.k)
+        self.dev = [i for i, n in enumerate(re.numels) if take(n)]
+        self.host = [i for i, n in enumerate(re.numels) if not take(n)]
+        self.off = np.asarray([re.offsets[i] for i in self.dev], np.int64)
+        self.num = np.asarray([re.numels[i] for i in self.dev], np.int64)
+        self.ks = None if self.kind == "kc" else [_topk_count(int(n), pipeline.p) for n in self.num]
+        hidx = [np.arange(re.offsets[i], re.offsets[i] + re.numels[i]) for i in self.host if re.numels[i]]
+        self._hidx = torch.from_numpy(np.concatenate(hidx).astype(np.int64)).to(re.device) if hidx else None
+
+    def _metadata(self, i, int_to_float, gz_md):
+        shape = list(self.re.shapes[i])
+        if self.kind == "kc":
+            return [{"int_list": shape, "int_to_float": int_to_float}, gz_md]
+        return [{"int_list": shape}, {"int_to_float": int_to_float}, gz_md]
+
+    def _host_deltas(self, delta, src, xs, weights, base_arena):
+        """The host-path tensors' deltas as the reference computes them, and
+        their base: {i: (delta, base or None)}.  Weighted average: np.average
+        itself on these few elements, minus the base in float64; geometric
+        median: the float64 aggregate minus the base; otherwise the float32
+        delta arena's elements."""
+        re = self.re
+        if self._hidx is None:
+            return {i: (np.zeros(re.shapes[i], np.float32), None) for i in self.host}
+        pick = lambda a: a.index_select(0, self._hidx)  # noqa: E731
+        wavg = isinstance(src, _WavgSeeds)
+        rows = ([pick(x) for x in xs] if wavg else [pick(delta)]) + ([pick(base_arena)] if base_arena is not None else [])
+        rows = torch.stack(rows).cpu().numpy()
+        agg64 = pick(src.agg).cpu().numpy() if not wavg and src.is_f64 else None
+        res, o = {}, 0
+        for i in self.host:
+            n, shape = re.numels[i], re.shapes[i]
+            part = lambda r: r[o:o + n].reshape(shape)  # noqa: E731
+            base = part(rows[-1]) if base_arena is not None else None
+            if wavg:
+                d = np.average([part(rows[c]) for c in range(len(xs))], weights=weights, axis=0)
+                d = d - base if base is not None else d
+            elif agg64 is not None:
+                d = part(agg64) - base if base is not None else part(agg64)
+            else:
+                d = part(rows[0])
+            res[i] = (d, base)
+            o += n
+        return res
+
+    def run(self, delta, src, xs, weights, base_arena, payloads, out):
+        re, pipe = self.re, self.pipeline
+        dev, T, nd = re.device, len(re.numels), len(self.dev)
+        seeds = [None] * T
+        draws = None
+        if self.kind != "stc" and nd:  # what kmeans_ranks draws per tensor, in tensor order
+            draws = np.random.randint(0, 2 ** 31 - 1, size=nd)
+            for i, sd in zip(self.dev, draws):
+                seeds[i] = int(sd)
+        x, maps, ranks, r3 = delta, [], None, None
+        if nd:
+            if self.kind != "kc":
+                x = re._empty_arena()
+                st = lossy.sparsify_topk_batch(delta, self.off, self.num, self.ks, x)
+            if self.kind == "stc":
+                if not np.isfinite(st["abs_sum"]).all():
+                    raise _lib.CodecError("stc: non-finite input")
+                tm = [ternary_map(int(n), int(st["n_pos"][t]), int(st["n_neg"][t]), float(st["abs_sum"][t]))
+                      for t, n in enumerate(self.num)]
+                maps, r3 = [m for m, _ in tm], [r for _, r in tm]
+                vrec = lossy.ternary_label_table(self.off, self.num, maps, r3, dev)
+            else:
+                vrec = lossy.LabelTable(nd, dev)
+                ranks = re._empty_arena() if payloads else None
+                uniq = lossy.kmeans_batch(x, self.off, self.num, self.k, n_init=self.k, seeds=draws,
+                                          value_f64=self.value_f64, ranks_out=ranks, value_out=vrec)[3]
+                maps = [{j: u for j, u in enumerate(uq)} for uq in uniq]
+        # the host path: the pipeline's own forward and backward (nothing of `out` is written yet)
+        result = [None] * T if payloads else None
+        new_host = []
+        for i, (d, base) in self._host_deltas(delta, src, xs, weights, base_arena).items():
+            payload, md = pipe.forward(d)
+            dec = pipe.backward(payload, [dict(m) for m in md])
+            new_host.append(np.asarray(base + dec if base is not None else dec, np.float32).reshape(-1))
+            if payloads:
+                result[i] = (payload, md)
+        if out is None:
+            out = re._empty_arena()
+        if nd:
+            lossy.label_apply(x, vrec, base_arena, out)
+        if self._hidx is not None:
+            out.index_copy_(0, self._hidx, torch.from_numpy(np.concatenate(new_host)).to(dev))
+        re._zero_gaps(out)
+        if payloads and nd:
+            if self.kind == "stc":
+                ranks = lossy.ternary_ranks_batch(x, self.off, self.num, r3, re._empty_arena())
+            for t, i in enumerate(self.dev):
+                o, n = int(self.off[t]), int(self.num[t])
+                payload, gz_md = self.gz.forward_device(ranks[o:o + n])
+                result[i] = (payload, self._metadata(i, maps[t], gz_md))
+        return out, result, seeds
+
+
 class RoundEnd:
     """Aggregator._prepare_trained for a whole model update (aggregator.py:780-865).
 
     pipeline: an openfl_amd EdenPipeline (its n_bits, dim_threshold and
-    seed_mode apply); shapes: the model's tensor shapes in the aggregator's
+    seed_mode apply), or a KCPipeline, SKCPipeline or STCPipeline (_LossyTail:
+    n_clusters <= 8; fused= does not apply; run()'s third value is then the
+    list of k-means seeds drawn, None where none was; a non-finite delta
+    raises CodecError before `out` is written); shapes: the model's tensor shapes in the aggregator's
     order.  Tensors live in flat float32 arenas, tensor i at offsets[i]
     (64-element aligned); arena() / pack() / view() make and read them.
     fused (default): without agg_out and with at most 16 collaborators the
@@ -548,12 +685,10 @@ class RoundEnd:
             raise _lib.CodecError(f"optimizer= belongs to the aggregations {ADAPTIVE_AGGREGATIONS}")
         self._opt = None   # (p, m, v) arenas after init_optimizer
         self._opt_step = 0
+        is_lossy = isinstance(pipeline, (KCPipeline, SKCPipeline, STCPipeline))
         tr = pipeline.transformers[0]
         self.transformer = tr
-        self.device = resolve_device(device) if device is not None else tr.eden.device
-        self.dim_threshold = tr.dim_threshold
-        self.seed_mode = tr.seed_mode
-        self.n_bits = tr.eden.nbits
+        self.device = resolve_device(device) if device is not None else (tr.device if is_lossy else tr.eden.device)
         self.shapes = [tuple(int(d) for d in s) for s in shapes]
         self.numels = [int(np.prod(s, dtype=np.int64)) for s in self.shapes]
         self.offsets, acc = [], 0
@@ -567,11 +702,30 @@ class RoundEnd:
         gaps.append(np.arange(acc, self.arena_numel))
         gap_idx = np.concatenate(gaps).astype(np.int64) if gaps else np.zeros(0, np.int64)
         self._gap_idx = torch.from_numpy(gap_idx).to(self.device) if gap_idx.size else None
-        self.big = [i for i, n in enumerate(self.numels) if n > self.dim_threshold]
         self.single = [i for i, n in enumerate(self.numels) if n == 1]
+        self._ws = _Scratch(self.device)
+        # what follows the delta: _tail(delta, seed source, collaborators, weights, base, payloads, out)
+        if is_lossy:
+            self.fused = False
+            self._tail = _LossyTail(self, pipeline).run
+        else:
+            self._init_eden(tr, fused)
+            self._tail = self._eden_tail
+        # pinned [collaborator pointers | weights | draws], reused after _args_done, and its device copy
+        self._host_args = self._dev_args = self._args_done = None
+        # geometric median: the chunk table of this layout, per-tensor state and
+        # (without agg_out) the float64 aggregate the delta and seeds come from
+        self._gm = _GmLayout(self.offsets, self.numels, self.device) if aggregation == "geometric_median" else None
+        self._gm_agg = None
+
+    def _init_eden(self, tr, fused):
+        """The Eden back end's plan and device tables (_device_seeds, _encode_apply)."""
+        self.dim_threshold = tr.dim_threshold
+        self.seed_mode = tr.seed_mode
+        self.n_bits = tr.eden.nbits
+        self.big = [i for i, n in enumerate(self.numels) if n > self.dim_threshold]
         self.plan = EdenPlan([self.numels[i] for i in self.big], self.n_bits,
                              elem_offsets=[self.offsets[i] for i in self.big]) if self.big else None
-        self._ws = _Scratch(self.device)
         self._codec_ws = None
         # tensors the codec does not touch (small, <= dim_threshold): their
         # apply_delta runs on these ranges (device tables)
@@ -591,7 +745,7 @@ class RoundEnd:
         # pass computes the delta from the collaborators' arenas itself, so the
         # delta arena is written only where something else reads it -- the
         # tensors the codec does not touch and the slices of <= 2^15 elements
-        self.fused = bool(fused) and self.plan is not None and aggregation == "weighted_average"
+        self.fused = bool(fused) and self.plan is not None and self.aggregation == "weighted_average"
         fz = list(rest)
         for t, i in enumerate(self.big):
             _, lens = slice_plan(self.numels[i])
@@ -601,12 +755,6 @@ class RoundEnd:
                     fz.append((xo, ln))
                 xo += ln
         self._fz = _RangeTable(sorted(fz), self.device)
-        # pinned [collaborator pointers | weights | draws], reused after _args_done, and its device copy
-        self._host_args = self._dev_args = self._args_done = None
-        # geometric median: the chunk table of this layout, per-tensor state and
-        # (without agg_out) the float64 aggregate the delta and seeds come from
-        self._gm = _GmLayout(self.offsets, self.numels, self.device) if aggregation == "geometric_median" else None
-        self._gm_agg = None
 
     # -- arenas --
     def arena(self):
@@ -668,7 +816,9 @@ class RoundEnd:
         float32 (the parameters after the step) and the step count rises by one.
         -> (new model arena, [(payload bytes, [metadata])] per tensor or None,
         seeds: a list with payloads, else the device int32 tensor -- without
-        payloads nothing synchronises with the host)."""
+        payloads nothing synchronises with the host).  With a lossy pipeline
+        the seeds are always the list of k-means seeds drawn (None per tensor
+        where none was) and the k-means synchronises."""
         xs = list(collab_arenas)
         for x in xs + ([base_arena] if base_arena is not None else []):
             self._check_arena(x)
@@ -680,9 +830,17 @@ class RoundEnd:
         with torch.cuda.device(self.device):
             # 1. the aggregate and its delta rounded to float32, by the aggregation's kernels
             delta, seed_source = getattr(self, "_delta_" + family)(xs, weights, base_arena, agg_out)
-            # 2. the seeds, 3. encode, (payloads), decode in place, apply
-            wavg = self._device_seeds(seed_source, xs, base_arena)
-            return self._encode_apply(delta, base_arena, payloads, out, wavg)
+            # what follows is the pipeline's: Eden -- 2. the seeds, 3. encode, (payloads), decode in
+            # place, apply; KC / SKC / STC -- _LossyTail
+            return self._tail(delta, seed_source, xs, weights, base_arena, payloads, out)
+
+    def _eden_tail(self, delta, seed_source, xs, weights, base_arena, payloads, out):
+        wavg = self._device_seeds(seed_source, xs, base_arena)
+        return self._encode_apply(delta, base_arena, payloads, out, wavg)
+
+    def _zero_gaps(self, out):
+        if self._gap_idx is not None:
+            out.index_fill_(0, self._gap_idx, 0.0)
 
     def _check_arena(self, x):
         if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= self.arena_numel):
@@ -849,6 +1007,5 @@ class RoundEnd:
                                                      out.data_ptr(), _stream(dev)))
             else:
                 out.copy_(delta)
-            if self._gap_idx is not None:
-                out.index_fill_(0, self._gap_idx, 0.0)
+            self._zero_gaps(out)
         return out, result, (seeds if payloads else self._seeds[:T])

@@ -235,6 +235,7 @@ struct BkmArgs {
     int32_t final_pass;
     int32_t pad_;
     uint64_t seed;
+    const uint64_t* seeds;   // [T] one seed per tensor, each run as a batch of one (else NULL: seed, tensor index mixed in)
     BkmState* st;
     uint32_t* hc;            // [T][4096] counts
     unsigned long long* hs;  // [T][4096] sums of (position inside the bin) * 2^32
@@ -498,7 +499,9 @@ __global__ __launch_bounds__(kBkmSeedNT) void k_bkm_seed(BkmArgs a) {
         return b;
     };
     // every thread draws the same numbers
-    uint64_t rs = (a.seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(t + 1)) ^ (0xD1B54A32D192ED03ull * (uint64_t)(run + 1))) | 1ull;
+    const uint64_t sd = a.seeds ? a.seeds[t] : a.seed;
+    const int tmix = a.seeds ? 0 : t;  // per-tensor seeds: the stream of tensor 0 of a one-tensor call
+    uint64_t rs = (sd ^ (0x9E3779B97F4A7C15ull * (uint64_t)(tmix + 1)) ^ (0xD1B54A32D192ED03ull * (uint64_t)(run + 1))) | 1ull;
     for (int q = 0; q < 4; ++q) bkm_rng(rs);
     const int trials = 2 + (int)log((double)k);  // sklearn's n_local_trials
     {
@@ -780,7 +783,11 @@ __global__ __launch_bounds__(kBkmAccNT) void k_bkm_label(BkmArgs a) {
 static_assert(sizeof(ofl_label_rec) == 80, "lossy.LabelTable.REC_BYTES");
 // each tensor's labelling rule as an ofl_label_rec (k <= 8): what k_bkm_label
 // applies, for the gzip encoder to apply as it loads the values
-__global__ __launch_bounds__(64) void k_bkm_tab(BkmArgs a, ofl_label_rec* tab) {
+// vtab: the same rule with each rank replaced by the float32 value the
+// reference's backward decodes it to -- `for key in map: data[data == key] =
+// map[key]` (kc_pipeline.py:79-83) with the map {i: uniq[i]} in order, so a
+// value equal to a later key is replaced again -- for ofl_label_apply
+__global__ __launch_bounds__(64) void k_bkm_tab(BkmArgs a, ofl_label_rec* tab, ofl_label_rec* vtab) {
     const int t = (int)(blockIdx.x * 64 + threadIdx.x);
     if (t >= a.ntensors) return;
     const BkmState& S = a.st[t];
@@ -791,7 +798,111 @@ __global__ __launch_bounds__(64) void k_bkm_tab(BkmArgs a, ofl_label_rec* tab) {
         r.mid[j] = j < 7 ? S.mids[j] : INFINITY;
         r.rank[j] = S.rank[j < a.k ? j : a.k - 1];
     }
-    tab[t] = r;
+    if (tab) tab[t] = r;
+    if (!vtab) return;
+    for (int j = 0; j < 8; ++j) {
+        float v = r.rank[j];
+        for (int i = 0; i < S.nuniq; ++i) v = v == (float)i ? (float)S.uniq[i] : v;
+        r.rank[j] = v;
+    }
+    vtab[t] = r;
+}
+
+// The round end's tail (ofl_label_apply): out = base + value of x's cluster,
+// the labelling rule of k_bkm_label (the > chain: a NaN takes cluster 0) on
+// value records.  The records live on the device, so the host does not know
+// the chunk count: a fixed grid, every workgroup builds the chunk -> tensor
+// table of bkm_range (first chunk of every record) in LDS and strides over the
+// 2^16-element chunks.  16-B loads and stores over the aligned middle, scalar
+// head and tail; the record's 16 floats stay in registers.
+constexpr int kLaMaxT = 4096;  // records per launch (the LDS table)
+// a record's rule in registers (scalars passed by value: kept in a closure or
+// an array they end up in LDS behind a computed index)
+struct LaRule { float m0, m1, m2, m3, m4, m5, m6, r0, r1, r2, r3, r4, r5, r6, r7; };
+DEVI float la_val(const LaRule q, float v) {
+    float o = q.r0;
+    o = v > q.m0 ? q.r1 : o;
+    o = v > q.m1 ? q.r2 : o;
+    o = v > q.m2 ? q.r3 : o;
+    o = v > q.m3 ? q.r4 : o;
+    o = v > q.m4 ? q.r5 : o;
+    o = v > q.m5 ? q.r6 : o;
+    o = v > q.m6 ? q.r7 : o;
+    return o;
+}
+// without a base the value itself (0 + v would turn a -0.0 into +0.0)
+template <bool BASE>
+DEVI float4 la_add(const LaRule q, float4 b, float4 v) {
+    const float4 d = make_float4(la_val(q, v.x), la_val(q, v.y), la_val(q, v.z), la_val(q, v.w));
+    return BASE ? make_float4(b.x + d.x, b.y + d.y, b.z + d.z, b.w + d.w) : d;
+}
+template <bool BASE>
+DEVI void la_one(const LaRule q, const float* xa, const float* base, float* out, int64_t i) {
+    const float d = la_val(q, xa[i]);
+    out[i] = BASE ? base[i] + d : d;
+}
+template <bool BASE>
+__global__ __launch_bounds__(kBkmAccNT) void k_label_apply(const float* xa, const ofl_label_rec* __restrict__ recs, int nt,
+                                                           const float* base, float* out) {
+    __shared__ int32_t first[kLaMaxT + 1];  // first[t] = chunks before record t
+    for (int t = threadIdx.x; t < nt; t += kBkmAccNT) {
+        const int64_t n = recs[t].end - recs[t].start;
+        first[t + 1] = n > 0 ? (int32_t)((n + kBkmChunk - 1) / kBkmChunk) : 0;
+    }
+    if (threadIdx.x == 0) first[0] = 0;
+    __syncthreads();
+    if (threadIdx.x < 64) {  // inclusive scan: lane l owns `per` consecutive entries
+        const int per = (nt + 63) / 64, lo = 1 + (int)threadIdx.x * per;
+        const int hi = lo + per < nt + 1 ? lo + per : nt + 1;
+        int32_t s = 0;
+        for (int i = lo; i < hi; ++i) s += first[i];
+        int32_t inc = s;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int32_t u = __shfl_up(inc, o, 64);
+            if ((int)threadIdx.x >= o) inc += u;
+        }
+        int32_t run = inc - s;
+        for (int i = lo; i < hi; ++i) { run += first[i]; first[i] = run; }
+    }
+    __syncthreads();
+    const int total = first[nt];
+    // x, base and out are indexed alike: 16-B accesses where they are aligned together
+    const uintptr_t px = reinterpret_cast<uintptr_t>(xa), po = reinterpret_cast<uintptr_t>(out);
+    const bool vec = (((px ^ po) | (BASE ? px ^ reinterpret_cast<uintptr_t>(base) : 0)) & 15u) == 0;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int c = blockIdx.x; c < total; c += gridDim.x) {
+        int lo = 0, hi = nt - 1;
+        while (lo < hi) {  // last record whose first chunk is <= c (empty records share their successor's)
+            const int mid = (lo + hi + 1) >> 1;
+            if (first[mid] <= c) lo = mid; else hi = mid - 1;
+        }
+        const int t = __builtin_amdgcn_readfirstlane(lo);
+        const ofl_label_rec* R = recs + t;
+        const int64_t rend = R->end;
+        const int64_t i0 = R->start + (int64_t)(c - first[t]) * kBkmChunk;
+        const int64_t i1 = i0 + kBkmChunk < rend ? i0 + kBkmChunk : rend;
+        const LaRule q = {R->mid[0], R->mid[1], R->mid[2], R->mid[3], R->mid[4], R->mid[5], R->mid[6], R->rank[0],
+                          R->rank[1], R->rank[2], R->rank[3], R->rank[4], R->rank[5], R->rank[6], R->rank[7]};
+        int64_t a4 = i0;
+        if (vec) while (a4 < i1 && (reinterpret_cast<uintptr_t>(xa + a4) & 15u)) ++a4; else a4 = i1;
+        const int64_t n4 = (i1 - a4) >> 2;
+        for (int64_t i = i0 + threadIdx.x; i < a4; i += kBkmAccNT) la_one<BASE>(q, xa, base, out, i);
+        for (int64_t i = a4 + 4 * n4 + threadIdx.x; i < i1; i += kBkmAccNT) la_one<BASE>(q, xa, base, out, i);
+        const float4* x4 = reinterpret_cast<const float4*>(xa + a4);
+        const float4* b4 = reinterpret_cast<const float4*>(BASE ? base + a4 : xa);
+        float4* o4 = reinterpret_cast<float4*>(out + a4);
+        // two 16-B loads per array in flight per lane (a lane reads its own
+        // elements before it writes them: out may alias x or base)
+        int64_t i = threadIdx.x;
+        for (; i + kBkmAccNT < n4; i += 2 * kBkmAccNT) {
+            const float4 v0 = x4[i], v1 = x4[i + kBkmAccNT];
+            const float4 b0 = BASE ? b4[i] : z4, b1 = BASE ? b4[i + kBkmAccNT] : z4;
+            o4[i] = la_add<BASE>(q, b0, v0);
+            o4[i + kBkmAccNT] = la_add<BASE>(q, b1, v1);
+        }
+        if (i < n4) o4[i] = la_add<BASE>(q, BASE ? b4[i] : z4, x4[i]);
+    }
 }
 
 // Batched reference backward (kc_pipeline.py:79-83 per tensor): tensor t's
@@ -1232,7 +1343,7 @@ size_t ofl_lossy_workspace_bytes(int64_t n) {
 }  // extern "C"
 namespace {
 struct BkmLayout {
-    size_t td, st, hc, hs, part, total;
+    size_t td, st, hc, hs, part, seeds, total;
     int64_t blocks;
 };
 BkmLayout bkm_layout(int T, const int64_t* numels) {
@@ -1245,7 +1356,8 @@ BkmLayout bkm_layout(int T, const int64_t* numels) {
     L.hc = L.st + al(sizeof(lossy::BkmState) * T);
     L.hs = L.hc + al(sizeof(uint32_t) * lossy::kBkmBins * T);
     L.part = L.hs + al(sizeof(unsigned long long) * lossy::kBkmBins * T);
-    L.total = L.part + al(sizeof(double) * 3 * lossy::kMaxK * (size_t)std::max<int64_t>(L.blocks, 1));
+    L.seeds = L.part + al(sizeof(double) * 3 * lossy::kMaxK * (size_t)std::max<int64_t>(L.blocks, 1));
+    L.total = L.seeds + al(sizeof(uint64_t) * T);
     return L;
 }
 template <int KM1>
@@ -1256,6 +1368,12 @@ template <int KM1>
 void bkm_launch_label(int64_t blocks, hipStream_t st, const lossy::BkmArgs& a) {
     hipLaunchKernelGGL(lossy::k_bkm_label<KM1>, dim3((unsigned)blocks), dim3(lossy::kBkmAccNT), 0, st, a);
 }
+// the batched k-means behind every entry point; seeds (host, [ntensors]): one
+// seed per tensor (ofl_kmeans1d_batch_seeds), else NULL and `seed` for all
+int bkm_run(int ntensors, const float* x_arena, const int64_t* offsets, const int64_t* numels, int k, int n_init,
+            uint64_t seed, const uint64_t* seeds, int max_exact, int value_f64, float* ranks_out,
+            ofl_label_rec* label_tab, ofl_label_rec* value_tab, double* centres, int64_t* counts, double* inertia,
+            int32_t* nuniq, double* uniq, void* ws, size_t ws_bytes, void* stream);
 }  // namespace
 extern "C" {
 
@@ -1276,8 +1394,42 @@ int ofl_kmeans1d_batch_tab(int ntensors, const float* x_arena, const int64_t* of
                            int n_init, uint64_t seed, int max_exact, int value_f64, float* ranks_out,
                            ofl_label_rec* label_tab, double* centres, int64_t* counts, double* inertia,
                            int32_t* nuniq, double* uniq, void* ws, size_t ws_bytes, void* stream) {
+    return bkm_run(ntensors, x_arena, offsets, numels, k, n_init, seed, nullptr, max_exact, value_f64, ranks_out,
+                   label_tab, nullptr, centres, counts, inertia, nuniq, uniq, ws, ws_bytes, stream);
+}
+
+int ofl_kmeans1d_batch_seeds(int ntensors, const float* x_arena, const int64_t* offsets, const int64_t* numels, int k,
+                             int n_init, const uint64_t* seeds, int max_exact, int value_f64, float* ranks_out,
+                             ofl_label_rec* label_tab, ofl_label_rec* value_tab, double* centres, int64_t* counts,
+                             double* inertia, int32_t* nuniq, double* uniq, void* ws, size_t ws_bytes, void* stream) {
+    if (!seeds) return lfail(OFL_EINVAL, "kmeans: one seed per tensor is required");
+    return bkm_run(ntensors, x_arena, offsets, numels, k, n_init, 0, seeds, max_exact, value_f64, ranks_out, label_tab,
+                   value_tab, centres, counts, inertia, nuniq, uniq, ws, ws_bytes, stream);
+}
+
+int ofl_label_apply(const float* x_arena, const ofl_label_rec* recs, int ntensors, const float* base, float* out,
+                    void* stream) {
+    if (!x_arena || !recs || !out || ntensors < 1) return lfail(OFL_EINVAL, "label_apply: bad arguments");
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    // two 1024-thread workgroups fill a CU; they stride over the chunks
+    for (int t0 = 0; t0 < ntensors; t0 += lossy::kLaMaxT)
+        hipLaunchKernelGGL(base ? lossy::k_label_apply<true> : lossy::k_label_apply<false>, dim3((unsigned)(2 * cus)),
+                           dim3(lossy::kBkmAccNT), 0, static_cast<hipStream_t>(stream), x_arena, recs + t0,
+                           std::min(ntensors - t0, lossy::kLaMaxT), base, out);
+    LHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+}  // extern "C"
+namespace {
+int bkm_run(int ntensors, const float* x_arena, const int64_t* offsets, const int64_t* numels, int k, int n_init,
+            uint64_t seed, const uint64_t* seeds, int max_exact, int value_f64, float* ranks_out,
+            ofl_label_rec* label_tab, ofl_label_rec* value_tab, double* centres, int64_t* counts, double* inertia,
+            int32_t* nuniq, double* uniq, void* ws, size_t ws_bytes, void* stream) {
     if (ntensors < 1 || !x_arena || !offsets || !numels) return lfail(OFL_EINVAL, "kmeans: empty batch");
-    if (label_tab) {
+    if (label_tab || value_tab) {
         if (k > 8) return lfail(OFL_EINVAL, "kmeans: label records need k <= 8");
         for (int t = 0; t < ntensors; ++t)
             if (offsets[t] < 0 || (t > 0 && offsets[t] < offsets[t - 1] + numels[t - 1]))
@@ -1314,11 +1466,13 @@ int ofl_kmeans1d_batch_tab(int ntensors, const float* x_arena, const int64_t* of
     a.n_init = n_init;
     a.value_f64 = value_f64 ? 1 : 0;
     a.seed = seed;
+    a.seeds = seeds ? reinterpret_cast<const uint64_t*>(w + L.seeds) : nullptr;
     a.st = reinterpret_cast<lossy::BkmState*>(w + L.st);
     a.hc = reinterpret_cast<uint32_t*>(w + L.hc);
     a.hs = reinterpret_cast<unsigned long long*>(w + L.hs);
     a.part = reinterpret_cast<double*>(w + L.part);
     LHIP(hipMemcpyAsync(w + L.td, td.data(), sizeof(lossy::BkmTensor) * ntensors, hipMemcpyHostToDevice, st));
+    if (seeds) LHIP(hipMemcpyAsync(w + L.seeds, seeds, sizeof(uint64_t) * ntensors, hipMemcpyHostToDevice, st));
     LHIP(hipMemsetAsync(w + L.st, 0, L.part - L.st, st));  // states + histograms
     const dim3 g((unsigned)L.blocks), b(lossy::kNT);
     hipLaunchKernelGGL(lossy::k_bkm_minmax, g, b, 0, st, a);
@@ -1337,7 +1491,8 @@ int ofl_kmeans1d_batch_tab(int ntensors, const float* x_arena, const int64_t* of
         else if (k <= 16) bkm_launch_label<15>(L.blocks, st, a);
         else bkm_launch_label<31>(L.blocks, st, a);
     }
-    if (label_tab) hipLaunchKernelGGL(lossy::k_bkm_tab, dim3((ntensors + 63) / 64), dim3(64), 0, st, a, label_tab);
+    if (label_tab || value_tab)
+        hipLaunchKernelGGL(lossy::k_bkm_tab, dim3((ntensors + 63) / 64), dim3(64), 0, st, a, label_tab, value_tab);
     LHIP(hipGetLastError());
     std::vector<lossy::BkmState> sh(ntensors);
     LHIP(hipMemcpyAsync(sh.data(), w + L.st, sizeof(lossy::BkmState) * ntensors, hipMemcpyDeviceToHost, st));
@@ -1356,6 +1511,8 @@ int ofl_kmeans1d_batch_tab(int ntensors, const float* x_arena, const int64_t* of
     }
     return OFL_OK;
 }
+}  // namespace
+extern "C" {
 
 size_t ofl_lut_decode_batch_workspace_bytes(int ntensors, int max_nk) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };

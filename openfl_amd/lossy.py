@@ -94,15 +94,88 @@ class LabelTable:
         self.buf = torch.empty(self.REC_BYTES * self.n, dtype=torch.uint8, device=device)
 
 
+    @classmethod
+    def from_rules(cls, starts, ends, mids, values, device):
+        """Records built on the host (one H2D): tensor t = arena elements
+        [starts[t], ends[t]), labelled values[t][j] for the first j with
+        x <= mids[t][j] (mids, values: [T, 8] float32)."""
+        T = len(starts)
+        rec = np.zeros(T, np.dtype([("start", "<i8"), ("end", "<i8"), ("mid", "<f4", 8), ("rank", "<f4", 8)]))
+        assert rec.dtype.itemsize == cls.REC_BYTES
+        rec["start"], rec["end"], rec["mid"], rec["rank"] = starts, ends, mids, values
+        tab = cls.__new__(cls)
+        tab.n = T
+        tab.buf = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(device)
+        return tab
+
+
+def decode_values(int_to_float, nranks=32):
+    """The float32 value of every rank 0 .. nranks - 1 under the reference's
+    backward, `for key in map: data[data == key] = map[key]` on a float32 array
+    (kc_pipeline.py:79-83), in the mapping's own order: a value equal to a
+    later key is replaced again.  Pure NumPy."""
+    v = np.arange(nranks, dtype=np.float32)
+    for key, val in int_to_float.items():
+        v = np.where(v == np.float32(key), np.float32(val), v)
+    return v
+
+
+_NEG_TINY = -np.float32(1e-45)   # the largest negative denormal: x > it  <=>  not (x < 0), for every non-NaN x
+
+
+def ternary_label_table(offsets, numels, maps, ranks3, device):
+    """TernaryTransformer's rule (stc_pipeline.py:105-130: x < 0, x == 0, x > 0
+    -> the ranks3[t] = (rank_neg, rank_zero, rank_pos) that ternary_ranks
+    writes) followed by the backward of maps[t] (its int_to_float), as value
+    records for label_apply: mid = (largest negative denormal, 0, +inf ...).
+    -0.0 and negative denormals land where ternary_ranks puts them; a NaN
+    takes the negative value (ternary_ranks: the zero rank), so callers refuse
+    non-finite input beforehand (sparsify_topk_batch's abs_sum)."""
+    T = len(numels)
+    mids = np.full((T, 8), np.inf, np.float32)
+    mids[:, 0], mids[:, 1] = _NEG_TINY, 0.0
+    vals = np.zeros((T, 8), np.float32)
+    for t in range(T):
+        dec = decode_values(maps[t])
+        vals[t, :3] = [dec[int(r)] for r in ranks3[t]]
+        vals[t, 3:] = vals[t, 2]
+    off = np.asarray(offsets, np.int64)
+    return LabelTable.from_rules(off, off + np.asarray(numels, np.int64), mids, vals, device)
+
+
+@_on_device
+def label_apply(x_arena, recs, base, out):
+    """out[i] = base[i] + value of x_arena[i]'s cluster (float32; the value
+    itself if base is None) for every element of every record of recs (a
+    LabelTable of value records: kmeans_batch's value_out, or
+    ternary_label_table) -- a lossy pipeline's decompress(compress(delta))
+    and apply_delta in one pass (ofl_label_apply).  out may be base or
+    x_arena; elements outside the records are not written."""
+    _check_dev(x_arena)
+    _check_dev(out)
+    if base is not None:
+        _check_dev(base)
+    if not recs.buf.is_cuda:
+        raise _lib.CodecError("label records must live on the device")
+    if recs.n:
+        _lib.check_lossy(_lib.lib().ofl_label_apply(x_arena.data_ptr(), recs.buf.data_ptr(), recs.n,
+                                                    base.data_ptr() if base is not None else None, out.data_ptr(),
+                                                    _stream(x_arena.device)))
+    return out
+
+
 @_on_device
 def kmeans_batch(x_arena, offsets, numels, k=6, n_init=6, seed=0, max_exact=8, value_f64=False, ranks_out=None,
-                 label_out=None):
+                 label_out=None, seeds=None, value_out=None):
     """Device k-means of many tensors of one float32 arena (ofl_kmeans1d_batch):
     tensor t = x_arena[offsets[t]:offsets[t] + numels[t]].  Writes float32
     ranks (np.unique order of the used centres, value dtype float64 if
     value_f64) into ranks_out (a device arena like x_arena) when given, and
     the labelling rules into label_out (a LabelTable; k <= 8, ascending
-    tensors) when given.
+    tensors) when given.  seeds (one per tensor, instead of seed): tensor t
+    runs bit for bit as a one-tensor call with seed=seeds[t]
+    (ofl_kmeans1d_batch_seeds); with them, value_out (a LabelTable) receives
+    the value records label_apply reads.
     -> (centres [T, k], counts [T, k], inertia [T], uniq: list of arrays)."""
     _check_dev(x_arena)
     L = _lib.lib()
@@ -118,17 +191,28 @@ def kmeans_batch(x_arena, offsets, numels, k=6, n_init=6, seed=0, max_exact=8, v
     uq = np.zeros((T, k), np.float64)
     if ranks_out is not None:
         _check_dev(ranks_out)
-    if label_out is not None:
-        if not label_out.buf.is_cuda:
-            raise _lib.CodecError("label_out must live on the device")
-        if label_out.n != T:
-            raise ValueError(f"label_out holds {label_out.n} records for {T} tensors")
-    _lib.check_lossy(L.ofl_kmeans1d_batch_tab(T, x_arena.data_ptr(), off.ctypes.data, num.ctypes.data, k, n_init,
-                                              int(seed), max_exact, 1 if value_f64 else 0,
-                                              ranks_out.data_ptr() if ranks_out is not None else None,
-                                              label_out.buf.data_ptr() if label_out is not None else None,
-                                              c.ctypes.data, cnt.ctypes.data, inertia.ctypes.data, nu.ctypes.data,
-                                              uq.ctypes.data, ws.data_ptr(), ws.numel(), _stream(x_arena.device)))
+    for name, tab in (("label_out", label_out), ("value_out", value_out)):
+        if tab is not None:
+            if not tab.buf.is_cuda:
+                raise _lib.CodecError(f"{name} must live on the device")
+            if tab.n != T:
+                raise ValueError(f"{name} holds {tab.n} records for {T} tensors")
+    head = (T, x_arena.data_ptr(), off.ctypes.data, num.ctypes.data, k, n_init)
+    tabs = (ranks_out.data_ptr() if ranks_out is not None else None,
+            label_out.buf.data_ptr() if label_out is not None else None)
+    tail = (c.ctypes.data, cnt.ctypes.data, inertia.ctypes.data, nu.ctypes.data, uq.ctypes.data, ws.data_ptr(),
+            ws.numel(), _stream(x_arena.device))
+    if seeds is not None:
+        sd = np.ascontiguousarray(seeds, np.uint64)
+        if sd.shape != (T,):
+            raise ValueError(f"{sd.size} seeds for {T} tensors")
+        _lib.check_lossy(L.ofl_kmeans1d_batch_seeds(*head, sd.ctypes.data, max_exact, 1 if value_f64 else 0, *tabs,
+                                                    value_out.buf.data_ptr() if value_out is not None else None,
+                                                    *tail))
+    else:
+        if value_out is not None:
+            raise ValueError("value_out needs per-tensor seeds")
+        _lib.check_lossy(L.ofl_kmeans1d_batch_tab(*head, int(seed), max_exact, 1 if value_f64 else 0, *tabs, *tail))
     dt = np.float64 if value_f64 else np.float32
     return c, cnt, inertia, [uq[t, :nu[t]].astype(dt) for t in range(T)]
 

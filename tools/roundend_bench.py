@@ -139,6 +139,128 @@ def adaptive(args, pipe, shapes, dev, collabs, w, base, out, nbytes, timed):
     print(json.dumps(line), flush=True)
 
 
+def lossy_round(args, shapes, dev, collabs, w, base, out, nbytes, timed):
+    """--pipeline kc | skc | stc: one JSON line with the round end's step time
+    (RoundEnd with that pipeline, weighted average) in windows alternated with
+    -- for kc -- the unfused composition on the same arenas (the same average
+    kernel, kmeans_batch with ranks_out, lut_decode_batch, ofl_apply_delta),
+    both with and without payloads, and the per-tensor host sequence; and, by
+    device events, ofl_label_apply alone (12 B/element) beside the three
+    kernels it replaces (28 B/element; k_bkm_label as the difference of a
+    k-means with and without ranks_out) and k_wavg_delta."""
+    import torch
+    from openfl_amd import _lib, lossy
+    from openfl_amd import aggregation as A
+    from openfl_amd import pipelines as P
+    C = len(collabs)
+    pipe = {"kc": P.KCPipeline, "skc": P.SKCPipeline, "stc": P.STCPipeline}[args.pipeline](p_sparsity=0.1, device=dev)
+    re = A.RoundEnd(pipe, shapes, dev)
+    tail = re._tail.__self__
+    n, L = re.arena_numel, _lib.lib()
+    nel = int(tail.num.sum())
+    ranks, dec = torch.empty_like(base), torch.empty_like(base)
+
+    def spread(ts):
+        ts = sorted(ts)
+        return {"min": round(1e3 * ts[0], 3), "median": round(1e3 * ts[len(ts) // 2], 3), "max": round(1e3 * ts[-1], 3),
+                "windows": len(ts)}
+
+    def unfused(payloads):
+        delta, _ = re._delta_weighted_average(collabs, w, base, None)
+        draws = np.random.randint(0, 2 ** 31 - 1, size=len(tail.dev))
+        uniq = lossy.kmeans_batch(delta, tail.off, tail.num, tail.k, n_init=tail.k, seeds=draws, value_f64=True,
+                                  ranks_out=ranks)[3]
+        maps = [{j: u for j, u in enumerate(uq)} for uq in uniq]
+        lossy.lut_decode_batch(ranks, tail.off, tail.num, maps, dec)
+        _lib.check_agg(L.ofl_apply_delta(base.data_ptr(), dec.data_ptr(), n, out.data_ptr(), A._stream(dev)))
+        if payloads:
+            return [tail.gz.forward_device(ranks[o:o + m]) for o, m in zip(tail.off.tolist(), tail.num.tolist())]
+
+    variants = {"round_end": lambda: re.run(collabs, w, base, payloads=False, out=out),
+                "round_end_payloads": lambda: re.run(collabs, w, base, payloads=True, out=out)}
+    if args.pipeline == "kc":
+        variants["unfused"] = lambda: unfused(False)
+        variants["unfused_payloads"] = lambda: unfused(True)
+    times = {k: [] for k in variants}
+    for _ in range(5):
+        for k, fn in variants.items():
+            pay = k.endswith("payloads")
+            times[k].append(timed(fn, max(1, args.steps // 2) if pay else args.steps, 1 if pay else args.warmup))
+    also = {k: {"ms_per_step": spread(v)} for k, v in times.items() if k != "round_end"}
+
+    if args.pipeline == "kc":
+        delta, _ = re._delta_weighted_average(collabs, w, base, None)
+        seeds = np.arange(1, len(tail.dev) + 1)
+        vrec = lossy.LabelTable(len(tail.dev), dev)
+        km = lambda r, v: lossy.kmeans_batch(delta, tail.off, tail.num, tail.k, n_init=tail.k, seeds=seeds,  # noqa: E731
+                                             value_f64=True, ranks_out=r, value_out=v)[3]
+        maps = [{j: u for j, u in enumerate(uq)} for uq in km(ranks, vrec)]
+        w64 = A._f64_weights(w, C)
+        wsum = A.weight_sum(w64, 1)
+        kernels = {
+            "label_apply": lambda: lossy.label_apply(delta, vrec, base, out),
+            "kmeans_with_ranks_out": lambda: km(ranks, None),
+            "kmeans_without_ranks_out": lambda: km(None, None),
+            "lut_decode_batch": lambda: lossy.lut_decode_batch(ranks, tail.off, tail.num, maps, dec),
+            "apply_delta": lambda: L.ofl_apply_delta(base.data_ptr(), dec.data_ptr(), n, out.data_ptr(), A._stream(dev)),
+            "wavg_delta": lambda: A._wavg_launch(collabs, w64, wsum, base, n, delta32=dec, device=dev),
+        }
+        ev = {k: [] for k in kernels}
+        for rep in range(args.kernel_reps + 2):
+            for k, fn in kernels.items():
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                fn()
+                e.record()
+                e.synchronize()
+                if rep >= 2:
+                    ev[k].append(s.elapsed_time(e) / 1e3)
+        med = {k: sorted(v)[len(v) // 2] for k, v in ev.items()}
+        label = med["kmeans_with_ranks_out"] - med["kmeans_without_ranks_out"]
+        three = label + med["lut_decode_batch"] + med["apply_delta"]
+
+        def rate(t, b):
+            return {"ms": round(1e3 * t, 4), "bytes_moved": b, "GBps": round(b / t / 1e9, 1),
+                    "frac_of_peak_hbm": round(b / t / 1e9 / PEAK_HBM_GBPS, 4)}
+        also["kernels_by_device_events"] = {
+            "repetitions": args.kernel_reps, "elements": nel,
+            "ofl_label_apply": dict(rate(med["label_apply"], 12 * nel), spread_ms=spread(ev["label_apply"])),
+            "three_kernels_it_replaces": dict(rate(three, 28 * nel), parts_ms={
+                "k_bkm_label_by_difference": round(1e3 * label, 4),
+                "lut_decode_batch_with_its_table_copies": round(1e3 * med["lut_decode_batch"], 4),
+                "k_apply": round(1e3 * med["apply_delta"], 4)}),
+            "k_wavg_delta": dict(rate(med["wavg_delta"], n * (4 * C + 4 + 4)), spread_ms=spread(ev["wavg_delta"])),
+            "kmeans_without_ranks_out_ms": round(1e3 * med["kmeans_without_ranks_out"], 3)}
+
+    if args.host_steps > 0:
+        from openfl_amd.tensor_codec import TensorCodec, TensorKey
+        tc = TensorCodec(pipe)
+        ch = [[re.view(a, i).cpu().numpy() for i in range(len(shapes))] for a in collabs]
+        bh = [re.view(base, i).cpu().numpy() for i in range(len(shapes))]
+        t0 = time.perf_counter()
+        for _ in range(args.host_steps):
+            for i in range(len(shapes)):
+                agg = np.average([c[i] for c in ch], weights=w, axis=0)
+                key = TensorKey(f"t{i}", "aggregator", 0, False, ("aggregated",))
+                dk, delta_h = tc.generate_delta(key, agg, bh[i])
+                ck, payload, md = tc.compress(dk, delta_h)
+                _, dec_h = tc.decompress(ck, payload, md)
+                tc.apply_delta(dk, dec_h, bh[i])
+        also["per_tensor_reference_call_pattern"] = {
+            "ms_per_step": round(1e3 * (time.perf_counter() - t0) / args.host_steps, 1)}
+    t = min(times["round_end"])
+    line = {"metric": f"GiB/s aggregator round end (average + delta + {args.pipeline.upper()} compress/decompress + "
+                      "apply), device-resident",
+            "value": round(nbytes / t / 2 ** 30, 3), "unit": "GiB/s", "n_gpus": 1, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": spread(times["round_end"]), "higher_is_better": True,
+            "dtype": "f32/f64", "data": "synthetic N(0, 0.01^2) updates and base, resident in HBM",
+            "config": {"workload": args.workload, "tensors": len(shapes), "bytes": nbytes, "collaborators": C,
+                       "pipeline": args.pipeline, "n_clusters": tail.k, "p_sparsity": 0.1,
+                       "host_path_tensors": len(tail.host)},
+            "also": also}
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="resnet50_fp32")
@@ -151,6 +273,10 @@ def main():
                     help="median / geometric_median / adam / yogi / adagrad: the round end with that aggregator "
                          "(never fused), its aggregation kernels alone, and the unfused weighted-average round "
                          "end beside it")
+    ap.add_argument("--pipeline", default="eden", choices=["eden", "kc", "skc", "stc"],
+                    help="kc / skc / stc: the round end of that lossy pipeline (weighted average) and, for kc, the "
+                         "unfused composition and ofl_label_apply beside the kernels it replaces")
+    ap.add_argument("--kernel-reps", type=int, default=20, help="--pipeline kc: device-event repetitions per kernel")
     args = ap.parse_args()
 
     import torch
@@ -183,6 +309,8 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / steps
 
+    if args.pipeline != "eden":
+        return lossy_round(args, shapes, dev, collabs, w, base, out, nbytes, timed)
     if args.aggregation in ("adam", "yogi", "adagrad"):
         return adaptive(args, pipe, shapes, dev, collabs, w, base, out, nbytes, timed)
     if args.aggregation != "weighted_average":
