@@ -53,6 +53,7 @@
 #include <vector>
 
 #include "eden_tables.h"
+#include "lds_exchange.h"
 #include "ofl_codec.h"
 #include "ofl_util.h"
 
@@ -191,10 +192,9 @@ DEVI float sgn_elem(float v, uint32_t e, int p, uint32_t b) {
 // ---------------------------------------------------------------------------
 // Register-layout engine
 // ---------------------------------------------------------------------------
-// A layout: tile of 2^nb elements; element bit r_i lives in register bit i
-// (5 or 6 register bits: 32 or 64 elements per thread); the other element
-// bits are the thread index, lowest first.
-struct Lay { int nb, r0, r1, r2, r3, r4, r5 = -1; };
+// struct Lay (lds_exchange.h): tile of 2^nb elements; element bit r_i lives in
+// register bit i (5 or 6 register bits: 32 or 64 elements per thread); the
+// other element bits are the thread index, lowest first.
 
 template <Lay L> struct LT {
     static constexpr int NR = L.r5 < 0 ? 5 : 6;
@@ -1817,6 +1817,11 @@ DEVI void row_locate(const KArgs& a, int t, int& si, uint32_t& tile, uint32_t* p
 // takes 77 KiB: two blocks per CU, no register prefetch (the other block
 // hides the loads).  Each thread quantises two runs of 32 contiguous
 // elements (bit 10 = 0, 1) and stores one 32-bit word per plane per run.
+// L4 -> L5 goes through the lane-linear image of lds_exchange.h in the same
+// buffer (ds_write_addtid_b32 stores, ds_read_b128 loads: L5's 32 registers
+// are the elements on L4's lanes 0..4); L3 -> L4 keeps the padded image, the
+// linear form saved 17 % of it alone and nothing measurable in the kernel
+// (profiles/lds_exchange_microbench.txt, profiles/lds_exchange_ab.txt).
 // ===========================================================================
 struct RowC2Set {
     static constexpr Lay L3{15, 5, 6, 7, 8, 9, 10}, L4{15, 11, 12, 13, 14, 9, 10}, L5{15, 0, 1, 2, 3, 4, 10};
@@ -1826,6 +1831,7 @@ struct RowC2Set {
 };
 constexpr size_t kRowC2Ex = (sizeof(float) * lds_floats(kRowLog - 1) + 15) & ~(size_t)15;
 constexpr size_t kRowC2Smem = kRowC2Ex + sizeof(QTab) + 64;
+static_assert(sizeof(float) * kLinBudget <= kRowC2Ex, "the lane-linear images share the padded image's buffer");
 
 template <Lay A, Lay B, int HB>
 DEVI void exchange_half_pad(float (&v)[64], float* s, uint32_t tid) {
@@ -1893,7 +1899,7 @@ __global__ __launch_bounds__(kRowNT, 4) void k_enc_rowC2(KArgs a) {
         stages<R::L3, R::F2c>(v);
         exchange_half_pad<R::L3, R::L4, R::HB>(v, s, tid);
         stages<R::L4, R::F2d>(v);
-        exchange_half_pad<R::L4, R::L5, R::HB>(v, s, tid);
+        exchange_half_lin<R::L4, R::L5, R::HB>(v, s, tid);
         stages<R::L5, R::F2e>(v);
         __builtin_amdgcn_sched_barrier(0);
         const float nu = sldf(a.nu, si);
@@ -1939,6 +1945,12 @@ struct RowA2Set {  // encode pass A, half bit 14: 0,1,11,12,13,14 | 2..6 | 10,7,
     static constexpr Lay A1 = RS::L1, A2{15, 2, 3, 4, 5, 6, 14}, A3{15, 10, 7, 8, 9, 6, 14};
     static constexpr uint32_t F1a = RS::F1a, F1b = bits_mask({2, 3, 4, 5, 6}), F1c = bits_mask({10, 7, 8, 9});
 };
+// Four of these exchanges go through the lane-linear image (lds_exchange.h),
+// as RowC2Set's L4 -> L5: RowA2Set's A1 -> A2 and DecC2Set's B1 -> B2 and
+// B2 -> B3 with 16-byte loads (the destination's registers 0, 1 lie on the
+// source's lanes 0, 1), DecA2Set's C2 -> C3 with dword loads.  They are the
+// ones the linear form makes at least a quarter cheaper alone; the others
+// keep the padded image (profiles/lds_exchange_microbench.txt).
 struct DecA2Set {  // decode pass A, half bit 5: 0..4 | 11,12,13,14,5 | 6..10
     static constexpr Lay C1 = RS::L5, C2{15, 11, 12, 13, 14, 9, 5}, C3{15, 6, 7, 8, 9, 10, 5};
     static constexpr uint32_t G1 = RS::F2e, G2 = bits_mask({11, 12, 13, 14, 5}), G3 = bits_mask({6, 7, 8, 9, 10});
@@ -2198,7 +2210,9 @@ __global__ __launch_bounds__(kRowNT, 4) void k_enc_rowA2(KArgs a) {
         else
             apply_signs_grouped<R::A1, !WAVG>(v, tile << kRowLog, base1, D.logp, b1, 1.0f);
         stages<R::A1, R::F1a>(v);
-        exchange_half_pad<R::A1, R::A2, 14>(v, s, tid);
+        // <true>'s weighted-average loads leave no register for the 16-byte reads' temporaries (it would spill)
+        if constexpr (WAVG) exchange_half_pad<R::A1, R::A2, 14>(v, s, tid);
+        else exchange_half_lin<R::A1, R::A2, 14>(v, s, tid);
         stages<R::A2, R::F1b>(v);
         exchange_half_pad<R::A2, R::A3, 14>(v, s, tid);
         stages<R::A3, R::F1c>(v);
@@ -2233,7 +2247,7 @@ __global__ __launch_bounds__(kRowNT, 4) void k_dec_rowA2(KArgs a) {
         stages<R::C1, R::G1>(v);
         exchange_half_pad<R::C1, R::C2, 5>(v, s, tid);
         stages<R::C2, R::G2>(v);
-        exchange_half_pad<R::C2, R::C3, 5>(v, s, tid);
+        exchange_half_lin<R::C2, R::C3, 5>(v, s, tid);
         stages<R::C3, R::G3>(v);
         store_ws_l<R::C3>(a, D, tile, base3, v);
     }
@@ -2258,9 +2272,9 @@ __global__ __launch_bounds__(kRowNT, 4) void k_dec_rowC2(KArgs a) {
         fetch_ws4<R::B1>(a, D, tile, true, base1, v, kDecC2LdAux);
         const uint32_t b1 = seed_b(sld(a.seeds, D.tensor));
         stages<R::B1, R::H1>(v);
-        exchange_half_pad<R::B1, R::B2, 10>(v, s, tid);
+        exchange_half_lin<R::B1, R::B2, 10>(v, s, tid);
         stages<R::B2, R::H2>(v);
-        exchange_half_pad<R::B2, R::B3, 10>(v, s, tid);
+        exchange_half_lin<R::B2, R::B3, 10>(v, s, tid);
         stages<R::B3, R::H3>(v);
         exchange_half_pad<R::B3, R::B4, 10>(v, s, tid);
         stages<R::B4, R::H4>(v);
