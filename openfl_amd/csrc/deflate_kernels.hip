@@ -434,9 +434,15 @@ DEVI uint32_t inf_entry(int s, int alpha) {
 }
 
 // canonical code from lengths (wave-parallel): counts and ranks by ballots,
-// the fast table filled by the symbols' lanes.  false: over-subscribed.
+// the fast table filled by the symbols' lanes.  false: over-subscribed, or
+// (check != kSetAny) incomplete by zlib's rule (inflate_table): unused code
+// space is an error unless no symbol has a code at all, or, for the literal
+// and distance sets only (kSetLone), the longest code is 1 bit.  The
+// code-length alphabet is never exempt (kSetFull).  The fixed codes leave
+// distance codes 30 and 31 out of their 5-bit space by definition (kSetAny).
+enum { kSetAny = 0, kSetLone = 1, kSetFull = 2 };
 template <typename C>
-DEVI bool inf_build(C& c, const uint8_t* lens, int n, int alpha) {
+DEVI bool inf_build(C& c, const uint8_t* lens, int n, int alpha, int check) {
     const int lane = (int)(threadIdx.x & 63u);
     const uint64_t below = (1ull << lane) - 1ull;
     for (int k = lane; k < C::kSize; k += 64) c.fast[k] = 0;
@@ -452,6 +458,12 @@ DEVI bool inf_build(C& c, const uint8_t* lens, int n, int alpha) {
     int left = 1;
 #pragma unroll
     for (int b = 1; b < 16; ++b) { left = (left << 1) - (int)cnt[b]; if (left < 0) return false; }
+    if (left > 0 && check != kSetAny) {  // wave-uniform: one test per table build
+        uint32_t longer = 0;             // codes of 2 bits or more
+#pragma unroll
+        for (int b = 2; b < 16; ++b) longer += cnt[b];
+        if (longer || (cnt[1] && check == kSetFull)) return false;
+    }
     if (lane < 16) c.cnt[lane] = (uint16_t)(lane ? cnt[lane] : 0u);
     uint32_t off[16], next[16];
     uint32_t o = 0, code = 0;
@@ -643,8 +655,8 @@ __global__ __launch_bounds__(64, OFL_INF_WAVES) void k_inflate_members(InfArgs a
             for (int i = lane; i < 320; i += 64)
                 S.lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5;
             __builtin_amdgcn_wave_barrier();
-            inf_build(S.lit, S.lens, 288, kAlphaLit);
-            inf_build(S.dist, S.lens + 288, 30, kAlphaDist);
+            inf_build(S.lit, S.lens, 288, kAlphaLit, kSetAny);
+            inf_build(S.dist, S.lens + 288, 30, kAlphaDist, kSetAny);
             inf_build_pairs(S);
         } else {  // dynamic: code-length code, then the literal/length and distance lengths
             topup();
@@ -658,7 +670,7 @@ __global__ __launch_bounds__(64, OFL_INF_WAVES) void k_inflate_members(InfArgs a
                 if (lane == 0) S.lens[c_clord[i]] = (uint8_t)v;
             }
             __builtin_amdgcn_wave_barrier();
-            if (!inf_build(S.lit, S.lens, 19, kAlphaPlain)) { err = kInfCorrupt; break; }
+            if (!inf_build(S.lit, S.lens, 19, kAlphaPlain, kSetFull)) { err = kInfCorrupt; break; }
             const int total = nlit + ndist;
             int i = 0;
             while (i < total) {
@@ -697,7 +709,7 @@ __global__ __launch_bounds__(64, OFL_INF_WAVES) void k_inflate_members(InfArgs a
             __builtin_amdgcn_wave_barrier();
             if (lane < 32) S.lens[288 + lane] = lane < ndist ? dl : 0;
             __builtin_amdgcn_wave_barrier();
-            if (!inf_build(S.lit, S.lens, nlit, kAlphaLit) || !inf_build(S.dist, S.lens + 288, ndist, kAlphaDist)) {
+            if (!inf_build(S.lit, S.lens, nlit, kAlphaLit, kSetLone) || !inf_build(S.dist, S.lens + 288, ndist, kAlphaDist, kSetLone)) {
                 err = kInfCorrupt;
                 break;
             }
@@ -2059,7 +2071,7 @@ __global__ __launch_bounds__(64) void k_tlz_ops(DecArgs a) {
             if (lane == 0) S.lens[c_clord[i]] = (uint8_t)v;
         }
         __builtin_amdgcn_wave_barrier();
-        if (!err && !inf_build(S.lit, S.lens, 19, kAlphaPlain)) err = kInfCorrupt;
+        if (!err && !inf_build(S.lit, S.lens, 19, kAlphaPlain, kSetFull)) err = kInfCorrupt;
         const int total = nlit + ndist;
         int i = 0;
         while (!err && i < total) {
@@ -2106,7 +2118,7 @@ __global__ __launch_bounds__(64) void k_tlz_ops(DecArgs a) {
             __builtin_amdgcn_wave_barrier();
             if (lane < 32) S.lens[288 + lane] = lane < ndist ? dl : 0;
             __builtin_amdgcn_wave_barrier();
-            if (!inf_build(S.lit, S.lens, nlit, kAlphaLit) || !inf_build(S.dist, S.lens + 288, ndist, kAlphaDist)) err = kInfCorrupt;
+            if (!inf_build(S.lit, S.lens, nlit, kAlphaLit, kSetLone) || !inf_build(S.dist, S.lens + 288, ndist, kAlphaDist, kSetLone)) err = kInfCorrupt;
         }
         if (!err && in.pos() != dbit + seg_bit(0)) err = kInfCorrupt;  // the ops start where the table says
     }
@@ -3146,7 +3158,9 @@ int ofl_gunzip_members(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, s
             z.avail_in = (uInt)m.in_len;
             z.next_out = dst + m.out;
             z.avail_out = m.isize;
-            if (inflate(&z, Z_FINISH) != Z_STREAM_END || z.total_out != m.isize ||
+            // every byte of the deflate data used, as the device inflate requires:
+            // a byte between the data and the trailer is not a gzip member
+            if (inflate(&z, Z_FINISH) != Z_STREAM_END || z.avail_in != 0 || z.total_out != m.isize ||
                 crc32(0L, dst + m.out, m.isize) != m.crc)
                 bad[t] = 1;
         }
