@@ -23,10 +23,12 @@ Reference functions exercised (citations are /root/reference-relative):
   openfl/pipelines/random_shift_pipeline.py:12-77  RandomShiftTransformer / Pipeline
   openfl/pipelines/no_compression_pipeline.py:10-15 NoCompressionPipeline
 
-Usage:  python tests/golden/make_golden.py [--only plain | --only designed]
+Usage:  python tests/golden/make_golden.py [--only plain | --only designed | --only topk]
         (writes tests/golden/*.npz, *.json; --only plain rewrites plain_golden.json only,
         --only designed writes eden_designed.json only: the reference's planes hashes and
-        scales on the designed inputs of tests/eden_exact.py)
+        scales on the designed inputs of tests/eden_exact.py; --only topk writes
+        topk_designed.json only: the reference's top-k and ternary results on the
+        tie-free designed inputs of tests/topk_cases.py)
 """
 import hashlib
 import importlib
@@ -308,6 +310,38 @@ def designed_fixtures(ref):
     return {"cases": cases}
 
 
+def topk_fixtures(ref):
+    """The reference's SparsityTransformer._topk_func, scattered as its forward
+    does, then its TernaryTransformer.forward, on the tie-free designed inputs of
+    tests/topk_cases.py (digit, shift-edge, infinity and p = 1.0 cases; the
+    reference's order among ties is introsort's, so tie cases stay out): per case
+    hashes of the sparse array and the ranks, the kept count, whether the +1e-7
+    rule fired, and the ternary table.  Data only; the tests rebuild the inputs."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from tests import topk_cases as C
+    stc, skc = ref["stc_pipeline"], ref["skc_pipeline"]
+    cases = []
+    for cid, build, args in C.fixture_cases():
+        x, k, _ = build(*args)
+        x = np.array(x)
+        topk, idx = stc.SparsityTransformer._topk_func(x, k)
+        topk2, idx2 = skc.SparsityTransformer._topk_func(x, k)
+        assert np.array_equal(idx, idx2) and np.array_equal(topk, topk2, equal_nan=True), cid
+        sparse = np.zeros(x.shape)
+        sparse[idx] = topk
+        assert np.array_equal(sparse.astype(np.float32).astype(np.float64), sparse), cid
+        # the +1e-7 rule on the reference's kept set (adding 1e-7 leaves values >= 2 unchanged,
+        # so the outputs alone do not always show it); where they do show it, they agree
+        shifted = bool(min(x[idx]) < 10e-8)
+        assert shifted or np.array_equal(np.asarray(topk), x[idx]), cid
+        ints, md = stc.TernaryTransformer().forward(sparse.copy())
+        cases.append({"id": cid, "n": int(x.size), "k": int(k), "kept": int(len(idx)), "shifted": bool(shifted),
+                      "sparse_sha256": sha(sparse.astype(np.float32).tobytes()),
+                      "int_to_float": [[int(r), float(v)] for r, v in md["int_to_float"].items()],
+                      "ranks_sha256": sha(np.asarray(ints, np.int32).tobytes())})
+    return {"cases": cases}
+
+
 def main():
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
     ref = _load_reference()
@@ -315,6 +349,11 @@ def main():
         with open(os.path.join(OUT, "eden_designed.json"), "w") as f:
             json.dump(designed_fixtures(ref), f, indent=1)
         print("wrote eden_designed.json")
+        return
+    if only == "topk":
+        with open(os.path.join(OUT, "topk_designed.json"), "w") as f:
+            json.dump(topk_fixtures(ref), f, indent=1)
+        print("wrote topk_designed.json")
         return
     with open(os.path.join(OUT, "plain_golden.json"), "w") as f:
         json.dump(plain_fixtures(ref), f, indent=1)

@@ -18,6 +18,7 @@ import torch
 
 from tests import golden_io
 from tests.kmeans_ref import kmeans_ref
+from tests.topk_cases import topk_ref as _topk_ref
 
 pytestmark = pytest.mark.gpu
 ARR, IDX = golden_io.lossy()
@@ -233,20 +234,6 @@ def test_kc_large_vs_sklearn():
     assert np.linalg.norm(y - x) / np.linalg.norm(x) < 0.3
 
 
-def _topk_ref(x, k):
-    """numpy restatement of SparsityTransformer._topk_func (skc_pipeline.py:
-    72-94) with ties at the k-th magnitude kept lowest index first."""
-    order = np.argsort(-np.abs(x), kind="stable")[:k]
-    kept = np.zeros(x.size, bool)
-    kept[order] = True
-    shift = np.float32(1e-7) if np.min(x[kept]) < 1e-7 else np.float32(0)
-    sp = np.where(kept, x + shift, np.float32(0)).astype(np.float32)
-    v = sp[kept]
-    return sp, {"n_pos": int(np.sum(v > 0)), "n_neg": int(np.sum(v < 0)), "n_zero": int(np.sum(v == 0)),
-                "abs_sum": float(np.sum(np.abs(v.astype(np.float64)))), "shifted": bool(shift),
-                "kept_min": np.min(x[kept])}
-
-
 def test_sparsify_topk_batch_vs_numpy():
     """Batched device top-k (ofl_sparsify_topk_batch) against the numpy
     restatement: ragged / unaligned offsets, ties straddling 64 Ki-element
@@ -293,6 +280,10 @@ def test_sparsify_topk_batch_vs_numpy():
         assert st["kept_min"][t] == ref["kept_min"], t
         assert abs(st["abs_sum"][t] - ref["abs_sum"]) <= 1e-12 * max(ref["abs_sum"], 1e-30), t
         assert res[1][1]["abs_sum"][t] == st["abs_sum"][t]
+    gap = np.ones(acc, bool)
+    for x, o in zip(xs, offs):
+        gap[o:o + x.size] = False
+    assert gap.sum() == 3 * len(xs) and np.all(out[gap] == np.float32(7.0))      # the gaps are not written
     # per-tensor entry point = batch of one
     sp1, st1 = lossy.sparsify_topk(torch.from_numpy(xs[0]).to(DEV), ks[0])
     np.testing.assert_array_equal(sp1.cpu().numpy(), out[offs[0]:offs[0] + xs[0].size])
