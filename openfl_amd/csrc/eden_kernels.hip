@@ -52,6 +52,8 @@
 #include <string>
 #include <vector>
 
+#include "eden_desc.h"
+#include "eden_plan.h"
 #include "eden_tables.h"
 #include "lds_exchange.h"
 #include "ofl_codec.h"
@@ -85,24 +87,8 @@ constexpr int kDecC2LdAux = 0;
 // had won at the 2 GiB waves of round 3, profiles/r03_nt_ab.txt)
 constexpr int kRowC2LdAux = 0;
 
-// ---------------------------------------------------------------------------
-// Descriptors (host-built once per plan, uploaded on first use)
-// ---------------------------------------------------------------------------
-struct SliceDesc {
-    int64_t x_off;      // encode: element offset of the slice's input in the fp32 arena
-    int64_t y_off;      // decode: element offset of the slice's output in the fp32 arena
-    int64_t ylen;       // decode: elements of this slice that land in the output
-    int64_t ws_off;     // element offset of the slice's intermediate in ws (large slices)
-    int64_t pl_off;     // byte offset of the slice's first byte of plane 0
-    int64_t pl_stride;  // bytes between planes of this tensor (= P_tot(t) / 8)
-    int64_t len;        // encode: valid input elements (<= P), zero padded to P
-    int32_t logp;
-    int32_t tensor;
-    int32_t scale_idx;
-    int32_t part_off;   // offset of this slice's partials (large slices)
-    int32_t perm;       // ws layout of a 2^25 slice: element bit 15 stored at bit 5 (ws_pos)
-    int32_t pad_;
-};
+// SliceDesc, the tile and group constants and the formats of the plan's
+// tables: eden_desc.h (shared with the planner, eden_plan.h)
 
 struct KArgs {
     const SliceDesc* d;
@@ -822,7 +808,6 @@ __global__ __launch_bounds__(1 << (P_LOG - 5)) void k_dec_small(KArgs a) {
 // body runs as its own workgroup or as one of 4 sub-blocks (all of one p) of
 // a small-set workgroup.
 // ===========================================================================
-constexpr int kTinyNT = 256;
 DEVI void fwht_lds_generic(float* s, int P, uint32_t tid) {
     for (int h = 1; h < P; h <<= 1) {
         for (int q = tid; q < (P >> 1); q += kTinyNT) {
@@ -937,7 +922,6 @@ __global__ __launch_bounds__(kTinyNT) void k_dec_tiny(KArgs a) {
 // small slices of 2^P elements, or up to 4 tiny slices of one p.  The waves of
 // sub-blocks past count end at once.
 // ===========================================================================
-constexpr int kSetNT = 1024;
 template <int P_LOG> struct SetSmem {
     static constexpr int SUB = kSetNT >> (P_LOG - 5);
     static constexpr size_t per = (SmallSmem<P_LOG>::data + SmallSmem<P_LOG>::tabs + 15) & ~(size_t)15;
@@ -1038,7 +1022,6 @@ struct RowSet6 {
                               F2d = bits_mask({11, 12, 13, 14}), F2e = bits_mask({0, 1, 2, 3, 4});
 };
 using RS = RowSet6;
-constexpr int kRowLog = 15;
 constexpr int kRowNT = 512;
 constexpr size_t kRowSmem = (sizeof(float) * lds_floats(kRowLog) + 15) & ~(size_t)15;
 // LDS after the exchange buffer: [tile table][8 wave partials][QTab | centroids]
@@ -1453,7 +1436,6 @@ __global__ __launch_bounds__(kRowNT) void k_dec_rowC(KArgs a) {
 // Column passes: tile = 2^M rows (index bits [lo, lo+M)) x 2^(15-M)
 // contiguous columns (bits [0, 15-M)), NT = 1024.  MID fuses F1 | D2 | F2.
 // ===========================================================================
-constexpr int kColLog = 15;
 constexpr int kColNT = 1024;
 constexpr size_t kColSmem = (sizeof(float) * lds_floats(kColLog) + 15) & ~(size_t)15;
 template <int M> struct ColSet {
@@ -1579,7 +1561,6 @@ __global__ __launch_bounds__(kColNT) void k_col(KArgs a) {
 // {M, list, tstart (both relative to the table), count, first block};
 // a.count = groups.  Height 6 needs col_body's exchange buffer: the launch
 // takes kColMultiSmem.
-constexpr int kColGroup = 5;
 constexpr size_t kColMultiSmem = kColSmem + kColTab;
 DEVI void col_multi_block(const KArgs& a, int b) {
     int g = 0;
@@ -2327,60 +2308,12 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
         if (e_ != hipSuccess) return fail(OFL_EHIP, std::string(#x " failed: ") + hipGetErrorString(e_)); \
     } while (0)
 
-struct Launch {
-    int kind;        // see enum below
-    int param;       // p (small) / M (column)
-    int lo;          // column passes
-    int mid;         // column: fused middle pass; decode row A: 8-byte plane words
-    int list_off;    // into d_list
-    int tstart_off;  // into d_tstart (multi-tile kernels), -1 otherwise
-    int count;       // list entries
-    int64_t blocks;  // grid size
-    int nu = 0;      // column: tile 0 of each slice writes the slice norm
-    int stream = 0;  // 0: the caller's stream, 1: the plan's side stream, 2: its small-slice stream
-    int join = 0;    // the caller's stream waits for the side stream before this launch
-    int btab_off = -1;  // column: per-block {slice, tile << 3 | group} table in ints
-    int ptab_off = -1;  // row: the paired table {slice, tile << 3 | pair} in ints (npair entries)
-    int npair = 0;
-    // a sub-wave launch of a split 5-pass slice (build_schedule): it covers
-    // expl_tiles tiles listed in btab_off ({slice, tile << 3}); row launches
-    // that apply D1 may take the paired list ptab_off (npair entries) instead
-    bool expl = false;
-    int64_t expl_tiles = 0;
-    bool nt = false;  // column: the intermediate streams through HBM (k_col6<..., true>)
-    int sset_off = -1;  // K_COLMSET: the small-set group table in ints
-    int sset_groups = 0;  // K_COLMSET: its groups (the launch's first blocks)
-    int64_t bytes_moved = 0;  // fp32/plane bytes this launch reads + writes (intermediates included)
-    int64_t bytes_alg = 0;    // its share of the SURVEY 8(d) algorithmic bytes (x/y fp32 + planes only)
-};
-enum Kind { K_TINY, K_SMALL, K_ROWA, K_ROWC, K_COL, K_FINAL, K_COLM, K_SSET, K_COLMSET };
+using eden::Launch;
 
 }  // namespace
 
 struct ofl_eden_plan {
-    int nbits = 8;
-    int ntensors = 0;
-    std::vector<ofl::SliceDesc> slices;
-    std::vector<int64_t> t_planes_off, t_planes_bytes;
-    std::vector<int32_t> t_first, t_nslices;
-    int64_t planes_bytes = 0;
-    int64_t ws_floats = 0;      // intermediates
-    int64_t part_floats = 0;    // partials
-    int64_t nlarge = 0;         // large slices (informational)
-    int64_t arena = 0;          // fp32 arena length: max over tensors of elem_offset + numel
-    // slice ids per kernel class (fixed by the batch) and the schedule built
-    // from them (build_schedule)
-    std::vector<int32_t> tiny, small[5], large;
-    int64_t wave_bytes = 0;     // intermediate bytes per wave of large slices; 0: one wave
-    int nstreams = 1;           // 2: waves alternate between the caller's and a side stream
-    int nwaves = 0;
-    int row2 = -1;              // row launches on the two-blocks-per-CU kernels: -1 auto, 0 never, 1 always
-    int pair = -1;              // their tile pairs sharing D1 words: -1 auto, 0 never, 1 whenever possible
-    int sset = -1;              // tiny / small slices in one small-set launch: -1 default (yes), 0 no, 1 yes
-    int fuse = -1;              // small-set groups fused into the column launch: -1 default (yes), 0 no, 1 yes
-    bool single = false;        // every launch on the caller's stream (no fork / join) -- K_COLMSET plans
-    std::vector<Launch> enc, dec;
-    std::vector<int32_t> ints;  // launch lists and tile prefixes (host copy)
+    eden::Plan p;               // the layout, the knobs and the schedule (host only: eden_plan.h)
     // profiling: events around every launch of every call while enabled
     bool prof = false;
     std::vector<std::vector<hipEvent_t>> prof_ev[2];  // [dec, enc][call][launch+1]
@@ -2388,7 +2321,7 @@ struct ofl_eden_plan {
     ofl::SliceDesc* d_slices = nullptr;
     int32_t* d_ints = nullptr;
     int device = -1;
-    int ncu = 256;              // persistent row launches: one block per CU
+    int ncu = 256;              // persistent row launches: one block per CU (eden::resolve)
     bool uploaded = false;
     std::mutex mu;
     hipStream_t side = nullptr;  // nstreams == 2: the device's shared side streams (shared_side_streams)
@@ -2399,169 +2332,85 @@ struct ofl_eden_plan {
 
 namespace {
 
-// Default large-slice schedule (see build_schedule):
-// waves the size of the 256 MiB Infinity Cache's working half on two streams,
-// with the two-blocks-per-CU row kernels (1-2 tiles per CU per wave).  Since
-// the additive-LCG signs these beat 2 GiB waves on the Llama-3-8B step (429-431
-// vs 426-427 GiB/s) and the 1 GiB set (470-474 vs 458-461); 256 MiB waves lose
-// (420-422 / 450-452), profiles/r06_sched_ab.txt.  Slices above the wave size
-// (the 2^29 ones) are waves of their own and keep the persistent kernels.
-constexpr int64_t kDefaultWaveMiB = 128;
-constexpr int64_t kDefaultStreams = 2;
-
-int64_t low_po2(int64_t n) { int64_t p = 1; while (p * 2 <= n) p *= 2; return n ? p : 0; }
-int64_t high_po2(int64_t n) { int64_t p = 1; while (p < n) p *= 2; return n ? p : 0; }
-int ilog2(int64_t v) { int l = 0; while ((1ll << l) < v) ++l; return l; }
-
-template <typename K>
-hipError_t launch(K kern, int64_t blocks, int threads, size_t shmem, hipStream_t st, const ofl::KArgs& a) {
-    if (blocks <= 0) return hipSuccess;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), shmem, st, a);
-    return hipGetLastError();
-}
-
-size_t small_smem(int p, bool enc) {
-    switch (p) {
-    case 11: return enc ? ofl::SmallSmem<11>::enc : ofl::SmallSmem<11>::dec;
-    case 12: return enc ? ofl::SmallSmem<12>::enc : ofl::SmallSmem<12>::dec;
-    case 13: return enc ? ofl::SmallSmem<13>::enc : ofl::SmallSmem<13>::dec;
-    case 14: return enc ? ofl::SmallSmem<14>::enc : ofl::SmallSmem<14>::dec;
-    default: return enc ? ofl::SmallSmem<15>::enc : ofl::SmallSmem<15>::dec;
-    }
-}
-
-hipError_t set_lds(const void* f, size_t bytes) {
-    return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-template <int P>
-hipError_t set_small_attr() {
-    hipError_t e = set_lds((const void*)ofl::k_enc_small<P>, ofl::SmallSmem<P>::enc);
-    return e != hipSuccess ? e : set_lds((const void*)ofl::k_dec_small<P>, ofl::SmallSmem<P>::dec);
-}
-
-size_t col_smem(int M, bool mid) { return (M > 5 ? ofl::kColSmem : 0) + (mid && M >= 3 ? ofl::kColTab : 0); }
+constexpr size_t col_smem(int M, bool mid) { return (M > 5 ? ofl::kColSmem : 0) + (mid && M >= 3 ? ofl::kColTab : 0); }
 
 // k_col6 tiles are 2^15 elements, two blocks per CU (2^16-element tiles with
 // 1024 threads measured slower on the 2^24 / 2^25 middle passes: 457 vs 432
 // us, 357 vs 307 us per launch)
-size_t col6_smem(int M, bool mid) { return (M > 6 ? ofl::col6_half<15>() : 0) + (mid ? ofl::col6_tab<15>() : 0); }
+constexpr size_t col6_smem(int M, bool mid) { return (M > 6 ? ofl::col6_half<15>() : 0) + (mid ? ofl::col6_tab<15>() : 0); }
 
-// Row launches of fewer than kRow2MaxTilesPerCu tiles per CU use the
-// two-blocks-per-CU kernels (k_enc_rowA2 / k_dec_rowA2 / k_dec_rowC2; outputs
-// bit-identical).  plan_mode (ofl_eden_plan_set_row2) 0: never, 1: always,
-// -1: below the threshold.
-constexpr int64_t kRow2MaxTilesPerCu = 5;
-bool use_row2(int64_t tiles, int ncu, int plan_mode) {
-    return plan_mode >= 0 ? plan_mode == 1 : tiles < kRow2MaxTilesPerCu * (int64_t)ncu;
-}
-
-// row launches up to this many tiles carry a per-tile table (8 B per tile)
-constexpr int64_t kRowTabMax = 1 << 16;
-// two-blocks-per-CU row launches of more tiles than block slots run tile
-// pairs sharing their D1 words (apply_signs_pair; plan_mode, see
-// ofl_eden_plan_set_pair, 0: never, 1: whenever the launch has a paired table)
-bool use_pair(const Launch& l, int ncu, int plan_mode) {
-    if (l.ptab_off < 0) return false;
-    return plan_mode >= 0 ? plan_mode == 1 : l.blocks > 2 * (int64_t)ncu;
-}
-
-// Single-level heights up to kColMultiMax share one k_col_multi launch per
-// wave.  Height 6 (2^21 slices) runs col_body<6> there (1024 threads, the
-// k_col arithmetic), not k_col6<6, true, 15>: the two differ in the order of
-// the row butterflies after D2, so their bytes differ slightly, and a
-// standalone height-6 launch uses k_col<6, true> too.
-constexpr int kColMultiMax = 6;
-// k_col6 (else k_col) for a column pass of this height: middle passes above
-// kColMultiMax, outer passes from 8 (measured: the 1024-thread k_col is ~4 %
-// faster on the plain M = 7 pass; the 5-pass slices' level-1 passes of heights
-// 5..7 run k_col)
-bool col6_for(int param, bool mid) { return param >= (mid ? kColMultiMax + 1 : 8); }
-
-// What a row launch (K_ROWA / K_ROWC) runs -- decided here alone, for run()
-// and for the names and details the plan reports (launch_name,
-// ofl_eden_plan_launch_detail).  wavg: the fused weighted-average encode's
-// pass A (k_enc_rowA2<true>), which never takes tile pairs.
-struct RowChoice {
-    bool two;      // the two-blocks-per-CU kernel (k_*_row?2), else the persistent one
-    bool expl;     // over an explicit tile list (a sub-wave of a split 5-pass slice)
-    bool paired;   // its table lists tile pairs
-    int tab_off;   // the table in ints that replaces the launch's default one (-1: keep)
-    int npair;     // table entries (KArgs::npair; 0: the launch's tile prefix)
-    int64_t grid;
+// The kernels a plan can launch: one entry per eden::KernelId, in the enum's
+// order (eden::resolve picks the id; the reported names are eden::kKernelName).
+// A kernel is launched with exactly these threads and dynamic LDS bytes, and
+// set_all_attrs raises the LDS limit of every entry that takes any.
+struct KernelEntry {
+    eden::KernelId id;
+    void (*fn)(ofl::KArgs);
+    int threads;
+    size_t lds;
 };
-RowChoice row_choice(const ofl_eden_plan* pl, const Launch& l, bool enc, bool wavg) {
-    const bool signs = l.kind == K_ROWA ? enc : !enc;  // the pass that applies D1
-    RowChoice c{false, l.expl, false, -1, 0, std::min<int64_t>(l.blocks, pl->ncu)};
-    if (l.expl) {
-        c.two = true;
-        c.paired = signs && !wavg && l.ptab_off >= 0;
-        c.tab_off = c.paired ? l.ptab_off : l.btab_off;
-        c.npair = c.paired ? l.npair : (int)l.expl_tiles;
-        c.grid = std::min<int64_t>(c.npair, 2 * pl->ncu);
-        return c;
-    }
-    // encode pass C has the two-blocks-per-CU kernel only (k_enc_rowC2)
-    if (l.kind == K_ROWA ? wavg || use_row2(l.blocks, pl->ncu, pl->row2)
-                         : enc || use_row2(l.blocks, pl->ncu, pl->row2)) {
-        c.two = true;
-        c.grid = std::min<int64_t>(l.blocks, 2 * pl->ncu);
-        if (signs && !wavg && use_pair(l, pl->ncu, pl->pair)) {
-            c.paired = true;
-            c.tab_off = l.ptab_off;
-            c.npair = l.npair;
-            c.grid = std::min<int64_t>(l.npair, 2 * pl->ncu);
-        }
-    }
-    return c;
+#define SMALL_ENTRIES(P)                                                                        \
+    {eden::ENC_SMALL##P, ofl::k_enc_small<P>, 1 << (P - 5), ofl::SmallSmem<P>::enc},            \
+    {eden::DEC_SMALL##P, ofl::k_dec_small<P>, 1 << (P - 5), ofl::SmallSmem<P>::dec}
+constexpr KernelEntry kKernels[] = {
+    {eden::ENC_TINY, ofl::k_enc_tiny, ofl::kTinyNT, 0},
+    {eden::DEC_TINY, ofl::k_dec_tiny, ofl::kTinyNT, 0},
+    {eden::ENC_SSET, ofl::k_enc_sset, ofl::kSetNT, ofl::kSetSmemEnc},
+    {eden::DEC_SSET, ofl::k_dec_sset, ofl::kSetNT, ofl::kSetSmemDec},
+    {eden::ENC_ROWA, ofl::k_enc_rowA, ofl::kRowNT, ofl::kRowSmemA},
+    {eden::DEC_ROWC, ofl::k_dec_rowC, ofl::kRowNT, ofl::kRowSmemA},
+    {eden::COL_MULTI, ofl::k_col_multi, ofl::kColNT, ofl::kColMultiSmem},
+    {eden::ENC_COLM_SET, ofl::k_enc_colm_set, ofl::kColNT, ofl::cmax(ofl::kSetSmemEnc, ofl::kColMultiSmem)},
+    {eden::DEC_COLM_SET, ofl::k_dec_colm_set, ofl::kColNT, ofl::cmax(ofl::kSetSmemDec, ofl::kColMultiSmem)},
+    {eden::ENC_ROWC2, ofl::k_enc_rowC2, ofl::kRowNT, ofl::kRowC2Smem},
+    {eden::DEC_ROWC2, ofl::k_dec_rowC2, ofl::kRowNT, ofl::kRow2Smem},
+    {eden::FINALIZE, ofl::k_finalize, 256, 0},
+    {eden::DEC_ROWA_A8, ofl::k_dec_rowA<true>, ofl::kRowNT, ofl::kRowSmemC},
+    {eden::DEC_ROWA, ofl::k_dec_rowA<false>, ofl::kRowNT, ofl::kRowSmemC},
+    {eden::ENC_ROWA2, ofl::k_enc_rowA2<false>, ofl::kRowNT, ofl::kRow2Smem},
+    {eden::ENC_ROWA2_WAVG, ofl::k_enc_rowA2<true>, ofl::kRowNT, ofl::kRow2Smem},
+    {eden::DEC_ROWA2_A8, ofl::k_dec_rowA2<true>, ofl::kRowNT, ofl::kRow2SmemC},
+    {eden::DEC_ROWA2, ofl::k_dec_rowA2<false>, ofl::kRowNT, ofl::kRow2SmemC},
+    {eden::COL_MID6, ofl::k_col<6, true>, ofl::kColNT, col_smem(6, true)},
+    {eden::COL_OUT6, ofl::k_col<6, false>, ofl::kColNT, col_smem(6, false)},
+    {eden::COL_OUT7, ofl::k_col<7, false>, ofl::kColNT, col_smem(7, false)},
+    {eden::COL6_MID7, ofl::k_col6<7, true, 15>, 512, col6_smem(7, true)},
+    {eden::COL6_MID8, ofl::k_col6<8, true, 15>, 512, col6_smem(8, true)},
+    {eden::COL6_MID9, ofl::k_col6<9, true, 15>, 512, col6_smem(9, true)},
+    {eden::COL6_MID10, ofl::k_col6<10, true, 15>, 512, col6_smem(10, true)},
+    {eden::COL6_MID7_NT, ofl::k_col6<7, true, 15, true>, 512, col6_smem(7, true)},
+    SMALL_ENTRIES(11), SMALL_ENTRIES(12), SMALL_ENTRIES(13), SMALL_ENTRIES(14), SMALL_ENTRIES(15),
+    {eden::COL_MID1, ofl::k_col<1, true>, ofl::kColNT, col_smem(1, true)},
+    {eden::COL_MID2, ofl::k_col<2, true>, ofl::kColNT, col_smem(2, true)},
+    {eden::COL_MID3, ofl::k_col<3, true>, ofl::kColNT, col_smem(3, true)},
+    {eden::COL_MID4, ofl::k_col<4, true>, ofl::kColNT, col_smem(4, true)},
+    {eden::COL_MID5, ofl::k_col<5, true>, ofl::kColNT, col_smem(5, true)},
+    {eden::COL_OUT5, ofl::k_col<5, false>, ofl::kColNT, col_smem(5, false)},
+};
+#undef SMALL_ENTRIES
+constexpr bool kernels_in_enum_order() {
+    for (int i = 0; i < eden::KERNEL_COUNT; ++i)
+        if (kKernels[i].id != i) return false;
+    return true;
 }
-
-// the kernel of a column launch (K_COL), for run() and launch_name
-enum ColKernel { COL_PLAIN, COL6, COL6_NT };
-ColKernel col_choice(const Launch& l) {
-    if (l.nt && l.param == 7 && l.mid) return COL6_NT;
-    return col6_for(l.param, l.mid != 0) ? COL6 : COL_PLAIN;
-}
+static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == eden::KERNEL_COUNT && kernels_in_enum_order(),
+              "kKernels: one entry per eden::KernelId, in the enum's order");
 
 hipError_t set_all_attrs() {
-    hipError_t e;
-    if ((e = set_small_attr<11>()) != hipSuccess) return e;
-    if ((e = set_small_attr<12>()) != hipSuccess) return e;
-    if ((e = set_small_attr<13>()) != hipSuccess) return e;
-    if ((e = set_small_attr<14>()) != hipSuccess) return e;
-    if ((e = set_small_attr<15>()) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_enc_sset, ofl::kSetSmemEnc)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_dec_sset, ofl::kSetSmemDec)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_enc_colm_set, std::max(ofl::kSetSmemEnc, ofl::kColMultiSmem))) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_dec_colm_set, std::max(ofl::kSetSmemDec, ofl::kColMultiSmem))) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_col_multi, ofl::kColMultiSmem)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_enc_rowA, ofl::kRowSmemA)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_enc_rowC2, ofl::kRowC2Smem)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_dec_rowA<true>, ofl::kRowSmemC)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_dec_rowA<false>, ofl::kRowSmemC)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_dec_rowC, ofl::kRowSmemA)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_enc_rowA2<false>, ofl::kRow2Smem)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_enc_rowA2<true>, ofl::kRow2Smem)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_dec_rowA2<true>, ofl::kRow2SmemC)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_dec_rowA2<false>, ofl::kRow2SmemC)) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_dec_rowC2, ofl::kRow2Smem)) != hipSuccess) return e;
-    // the column kernels a plan can launch (run(), K_COL) that exchange through LDS
-    if ((e = set_lds((const void*)ofl::k_col<6, true>, col_smem(6, true))) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_col<6, false>, col_smem(6, false))) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_col<7, false>, col_smem(7, false))) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_col6<7, true, 15>, col6_smem(7, true))) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_col6<8, true, 15>, col6_smem(8, true))) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_col6<9, true, 15>, col6_smem(9, true))) != hipSuccess) return e;
-    if ((e = set_lds((const void*)ofl::k_col6<10, true, 15>, col6_smem(10, true))) != hipSuccess) return e;
-    return set_lds((const void*)ofl::k_col6<7, true, 15, true>, col6_smem(7, true));
+    for (const KernelEntry& k : kKernels) {
+        if (k.lds == 0) continue;
+        const hipError_t e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller) {
     const hipError_t attrs_err = ofl_util::per_device_once([] { return set_all_attrs(); });
     if (attrs_err != hipSuccess) return fail(OFL_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(attrs_err));
-    const std::vector<Launch>& L = enc ? pl->enc : pl->dec;
+    const std::vector<Launch>& L = enc ? pl->p.enc : pl->p.dec;
     // waves on the side stream fork from and join back into the caller's stream
-    const bool two = pl->side != nullptr && !pl->single;
+    const bool two = pl->side != nullptr && !pl->p.single;
     std::unique_lock<std::mutex> lk(pl->run_mu, std::defer_lock);
     if (two) {
         lk.lock();
@@ -2570,7 +2419,6 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
         if (pl->side2) HIP_TRY(hipStreamWaitEvent(pl->side2, pl->ev_fork, 0));
     }
     const hipStream_t streams[3] = {caller, two ? pl->side : caller, pl->side2 ? pl->side2 : caller};
-    bool joined = !two;
     std::vector<hipEvent_t>* evs = nullptr;
     if (pl->prof) {  // one event before and one after every launch, on its stream
         std::lock_guard<std::mutex> g(pl->mu);
@@ -2583,609 +2431,95 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
             evs->push_back(e);
         }
     }
+    // the two facts of the call that choose among a launch's kernels
+    const bool wavg = base.wx != nullptr;
+    const bool planes8 = (reinterpret_cast<uintptr_t>(base.pin) & 7u) == 0;
     for (size_t li = 0; li < L.size(); ++li) {
         const Launch& l = L[li];
-        if (l.join && !joined) {
-            HIP_TRY(hipEventRecord(pl->ev_join, pl->side));
-            HIP_TRY(hipStreamWaitEvent(caller, pl->ev_join, 0));
-            joined = true;
-        }
+        eden::Resolved r;
+        if (const char* err = eden::resolve(pl->p, l, enc, pl->ncu, wavg, planes8, r)) return fail(OFL_EINVAL, err);
+        const KernelEntry& k = kKernels[r.id];
         const hipStream_t st = streams[l.stream];
         ofl::KArgs a = base;
         a.list = pl->d_ints + l.list_off;
         a.tstart = l.tstart_off >= 0 ? pl->d_ints + l.tstart_off : nullptr;
-        a.btab = l.btab_off >= 0 ? pl->d_ints + l.btab_off : nullptr;
+        a.btab = r.tab_off >= 0 ? pl->d_ints + r.tab_off : nullptr;
         a.count = l.count;
         a.lo = l.lo;
         a.do_nu = l.nu;
-        a.npair = 0;
-        if (evs) HIP_TRY(hipEventRecord((*evs)[2 * li], st));
-        hipError_t e = hipSuccess;
-        switch (l.kind) {
-        case K_TINY:
-            e = enc ? launch(ofl::k_enc_tiny, l.blocks, ofl::kTinyNT, 0, st, a)
-                    : launch(ofl::k_dec_tiny, l.blocks, ofl::kTinyNT, 0, st, a);
-            break;
-        case K_SSET:
-            e = enc ? launch(ofl::k_enc_sset, l.blocks, ofl::kSetNT, ofl::kSetSmemEnc, st, a)
-                    : launch(ofl::k_dec_sset, l.blocks, ofl::kSetNT, ofl::kSetSmemDec, st, a);
-            break;
-        case K_SMALL: {
-            const int p = l.param;
-            const int nt = 1 << (p - 5);
-            const size_t sm = small_smem(p, enc);
-#define SMALLCASE(PP)                                                                         \
-    case PP:                                                                                  \
-        e = enc ? launch(ofl::k_enc_small<PP>, l.blocks, nt, sm, st, a)                       \
-                : launch(ofl::k_dec_small<PP>, l.blocks, nt, sm, st, a);                      \
-        break;
-            switch (p) {
-                SMALLCASE(11) SMALLCASE(12) SMALLCASE(13) SMALLCASE(14) SMALLCASE(15)
-            default: return fail(OFL_EINVAL, "small slice size out of range");
-            }
-#undef SMALLCASE
-            break;
-        }
-        case K_ROWA: {
-            const bool a8 = l.mid && (reinterpret_cast<uintptr_t>(base.pin) & 7u) == 0;
-            const RowChoice rc = row_choice(pl, l, enc, enc && base.wx);
-            if (rc.tab_off >= 0) a.btab = pl->d_ints + rc.tab_off;
-            a.npair = rc.npair;
-            if (rc.two)
-                e = enc ? (base.wx ? launch(ofl::k_enc_rowA2<true>, rc.grid, ofl::kRowNT, ofl::kRow2Smem, st, a)
-                                   : launch(ofl::k_enc_rowA2<false>, rc.grid, ofl::kRowNT, ofl::kRow2Smem, st, a))
-                        : a8 ? launch(ofl::k_dec_rowA2<true>, rc.grid, ofl::kRowNT, ofl::kRow2SmemC, st, a)
-                             : launch(ofl::k_dec_rowA2<false>, rc.grid, ofl::kRowNT, ofl::kRow2SmemC, st, a);
-            else
-                e = enc ? launch(ofl::k_enc_rowA, rc.grid, ofl::kRowNT, ofl::kRowSmemA, st, a)
-                        : a8 ? launch(ofl::k_dec_rowA<true>, rc.grid, ofl::kRowNT, ofl::kRowSmemC, st, a)
-                             : launch(ofl::k_dec_rowA<false>, rc.grid, ofl::kRowNT, ofl::kRowSmemC, st, a);
-            break;
-        }
-        case K_ROWC: {
-            const RowChoice rc = row_choice(pl, l, enc, false);
-            if (rc.tab_off >= 0) a.btab = pl->d_ints + rc.tab_off;
-            a.npair = rc.npair;
-            if (enc)  // always two blocks per CU (row_choice)
-                e = launch(ofl::k_enc_rowC2, rc.grid, ofl::kRowNT, ofl::kRowC2Smem, st, a);
-            else
-                e = rc.two ? launch(ofl::k_dec_rowC2, rc.grid, ofl::kRowNT, ofl::kRow2Smem, st, a)
-                           : launch(ofl::k_dec_rowC, rc.grid, ofl::kRowNT, ofl::kRowSmemA, st, a);
-            break;
-        }
-        case K_COL: {
-            const ColKernel ck = col_choice(l);
-            // build_schedule makes middle passes of heights 1..10 (k_col to
-            // 6, k_col6 above) and outer passes, the level-1 halves of the
-            // two-level slices 2^26..2^29, of heights 5..7 (k_col)
-            if (ck == COL6_NT) {
-                e = launch(ofl::k_col6<7, true, 15, true>, l.blocks, 512, col6_smem(7, true), st, a);
-                break;
-            }
-            if (ck == COL6) {
-                const size_t sm = col6_smem(l.param, l.mid != 0);
-#define COL6CASE(MM) \
-    case MM: e = launch(ofl::k_col6<MM, true, 15>, l.blocks, 512, sm, st, a); break;
-                switch (l.mid ? l.param : 0) {
-                    COL6CASE(7) COL6CASE(8) COL6CASE(9) COL6CASE(10)
-                default: return fail(OFL_EINVAL, "column pass height out of range");
-                }
-#undef COL6CASE
-                break;
-            }
-            const size_t sm = col_smem(l.param, l.mid != 0);
-#define COLCASE(MM, MIDV) \
-    case MM: e = launch(ofl::k_col<MM, MIDV>, l.blocks, ofl::kColNT, sm, st, a); break;
-            if (l.mid) {
-                switch (l.param) {
-                    COLCASE(1, true) COLCASE(2, true) COLCASE(3, true) COLCASE(4, true) COLCASE(5, true) COLCASE(6, true)
-                default: return fail(OFL_EINVAL, "column pass height out of range");
-                }
-            } else {
-                switch (l.param) {
-                    COLCASE(5, false) COLCASE(6, false) COLCASE(7, false)
-                default: return fail(OFL_EINVAL, "column pass height out of range");
-                }
-            }
-#undef COLCASE
-            break;
-        }
-        case K_FINAL: e = launch(ofl::k_finalize, l.blocks, 256, 0, st, a); break;
-        case K_COLM: e = launch(ofl::k_col_multi, l.blocks, ofl::kColNT, ofl::kColMultiSmem, st, a); break;
-        case K_COLMSET:
+        a.npair = r.npair;
+        if (l.sset_off >= 0) {  // K_COLMSET
             a.sset = pl->d_ints + l.sset_off;
             a.sset_first = (int32_t)l.sset_groups;
-            e = enc ? launch(ofl::k_enc_colm_set, l.blocks, ofl::kColNT, std::max(ofl::kSetSmemEnc, ofl::kColMultiSmem), st, a)
-                    : launch(ofl::k_dec_colm_set, l.blocks, ofl::kColNT, std::max(ofl::kSetSmemDec, ofl::kColMultiSmem), st, a);
-            break;
         }
-        if (e != hipSuccess) return fail(OFL_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
+        if (evs) HIP_TRY(hipEventRecord((*evs)[2 * li], st));
+        if (r.grid > 0) {
+            hipLaunchKernelGGL(k.fn, dim3((unsigned)r.grid), dim3(k.threads), k.lds, st, a);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return fail(OFL_EHIP, std::string("kernel launch failed: ") + hipGetErrorString(e));
+        }
         if (evs) HIP_TRY(hipEventRecord((*evs)[2 * li + 1], st));
     }
-    if (!joined) {
+    if (two) {
         HIP_TRY(hipEventRecord(pl->ev_join, pl->side));
         HIP_TRY(hipStreamWaitEvent(caller, pl->ev_join, 0));
-    }
-    if (two && pl->side2) {
-        HIP_TRY(hipEventRecord(pl->ev_join2, pl->side2));
-        HIP_TRY(hipStreamWaitEvent(caller, pl->ev_join2, 0));
+        if (pl->side2) {
+            HIP_TRY(hipEventRecord(pl->ev_join2, pl->side2));
+            HIP_TRY(hipStreamWaitEvent(caller, pl->ev_join2, 0));
+        }
     }
     return OFL_OK;
-}
-
-std::string launch_name(const ofl_eden_plan* pl, const Launch& l, bool enc) {
-    const char* d = enc ? "enc" : "dec";
-    switch (l.kind) {
-    case K_TINY: return std::string("ofl::k_") + d + "_tiny";
-    case K_SSET: return std::string("ofl::k_") + d + "_sset";
-    case K_SMALL: return std::string("ofl::k_") + d + "_small<" + std::to_string(l.param) + ">";
-    case K_ROWA: return std::string("ofl::k_") + d + (row_choice(pl, l, enc, false).two ? "_rowA2" : "_rowA");
-    case K_ROWC: return std::string("ofl::k_") + d + (row_choice(pl, l, enc, false).two ? "_rowC2" : "_rowC");
-    case K_COL: {
-        const std::string mp = std::to_string(l.param) + ", " + (l.mid ? "true" : "false");
-        switch (col_choice(l)) {
-        case COL6_NT: return "ofl::k_col6<" + mp + ", 15, true>";
-        case COL6: return "ofl::k_col6<" + mp + ", 15>";
-        default: return "ofl::k_col<" + mp + ">";
-        }
-    }
-    case K_COLM: return "ofl::k_col_multi";
-    case K_COLMSET: return std::string("ofl::k_") + d + "_colm_set";
-    default: return "ofl::k_finalize";
-    }
-}
-
-// Large slices run in waves of at most wave_bytes of intermediates (a bigger
-// slice is a wave of its own).  A wave runs row pass A, its column passes and
-// row pass C back to back, so its intermediates are re-read while they still
-// sit in the 256 MiB Infinity Cache; waves share nstreams workspace buffers
-// (wave w: buffer and stream w % nstreams).  The scales are finalised once,
-// after every wave.
-void build_schedule(ofl_eden_plan* pl) {
-    std::vector<int32_t>& ints = pl->ints;
-    ints.clear();
-    pl->enc.clear();
-    pl->dec.clear();
-    auto add_list = [&](const std::vector<int32_t>& l) {
-        const int o = (int)ints.size();
-        ints.insert(ints.end(), l.begin(), l.end());
-        return o;
-    };
-    auto add_prefix = [&](const std::vector<int32_t>& l, int log_tile, int64_t& total) {
-        const int o = (int)ints.size();
-        int64_t acc = 0;
-        for (int32_t si : l) { ints.push_back((int32_t)acc); acc += 1ll << (pl->slices[si].logp - log_tile); }
-        ints.push_back((int32_t)acc);
-        total = acc;
-        return o;
-    };
-    std::vector<Launch> common;
-    const bool sset = pl->sset != 0;
-    if (sset) {
-        // one small-set launch: groups of one size, largest first; table of
-        // {P (0: tiny), slice-list offset (from the table), count} per block
-        std::vector<std::array<int32_t, 3>> groups;
-        std::vector<int32_t> ids;
-        auto add_groups = [&](int P, const std::vector<int32_t>& sl, int per) {
-            for (size_t i = 0; i < sl.size(); i += per) {
-                const int c = (int)std::min<size_t>(per, sl.size() - i);
-                groups.push_back({P, (int32_t)ids.size(), c});
-                ids.insert(ids.end(), sl.begin() + i, sl.begin() + i + c);
-            }
-        };
-        for (int k = 4; k >= 0; --k) add_groups(11 + k, pl->small[k], ofl::kSetNT >> (6 + k));
-        for (int p = 10; p >= 0; --p) {  // tiny slices: groups of one p (same barrier count)
-            std::vector<int32_t> sl;
-            for (int32_t si : pl->tiny) if (pl->slices[si].logp == p) sl.push_back(si);
-            add_groups(0, sl, ofl::kSetNT / ofl::kTinyNT);
-        }
-        if (!groups.empty()) {
-            const int o = (int)ints.size();
-            const int nt = 3 * (int)groups.size();
-            for (auto& g : groups) { ints.push_back(g[0]); ints.push_back(g[1] + nt); ints.push_back(g[2]); }
-            ints.insert(ints.end(), ids.begin(), ids.end());
-            common.push_back({K_SSET, 0, 0, 0, o, -1, (int)groups.size(), (int64_t)groups.size()});
-        }
-    } else {
-        if (!pl->tiny.empty())
-            common.push_back({K_TINY, 0, 0, 0, add_list(pl->tiny), -1, (int)pl->tiny.size(), (int64_t)pl->tiny.size()});
-        for (int k = 0; k < 5; ++k)
-            if (!pl->small[k].empty())
-                common.push_back({K_SMALL, 11 + k, 0, 0, add_list(pl->small[k]), -1, (int)pl->small[k].size(),
-                                  (int64_t)pl->small[k].size()});
-    }
-    for (auto& D : pl->slices) D.perm = 0;
-    std::vector<std::vector<int32_t>> waves;
-    int64_t cap = pl->wave_bytes > 0 ? pl->wave_bytes / 4 : INT64_MAX;
-    int64_t tot = 0;
-    for (int32_t si : pl->large) tot += 1ll << pl->slices[si].logp;
-    // more than one wave by size: the large slices largest first (stable), so
-    // in-order packing fills each wave with slices of one size -- power-of-two
-    // sizes pack whole waves, one column launch per wave (batch order and
-    // smallest first both lost, profiles/r06_sort_roll_ab.txt).
-    // Llama-3-8B: 210 waves of 1024 tiles (but the two 2^29 ones), 637
-    // launches per direction instead of 258 waves of 512-1024 tiles and 909
-    // launches; 434.8-435.4 -> 445.7-448.8 GiB/s
-    std::vector<int32_t> sorted_large;
-    if (tot > cap) {
-        sorted_large = pl->large;
-        std::stable_sort(sorted_large.begin(), sorted_large.end(),
-                         [&](int32_t x, int32_t y) { return pl->slices[x].logp > pl->slices[y].logp; });
-    }
-    const std::vector<int32_t>& large = sorted_large.empty() ? pl->large : sorted_large;
-    // two streams: at least two waves, so both streams have work -- unless
-    // every large slice fits one wave and no small-slice launches could use
-    // the second stream (at 2 GiB waves the 1 GiB set ran one wave on one
-    // stream, 2.24 vs 2.29 ms; ResNet-50 keeps its two waves beside the small slices: 360
-    // vs 369 us with one wave)
-    // With the small-set launch a plan that fits one wave keeps it whole: the
-    // one small-set launch runs beside it on the side stream (ResNet-50 0.288
-    // vs 0.309 ms with two waves, profiles/r03_resnet50_sset_onewave_ab.txt)
-    const bool split = (!common.empty() && !sset) || tot > cap;
-    // the split only feeds the second stream (everything fits one wave):
-    // exactly two waves, cut where the halves are closest (in-order packing
-    // against a half-total cap can leave a third wave behind the first on the
-    // same stream -- ResNet-50: 417 vs 353 tiles per stream)
-    int64_t cut = -1;
-    if (pl->nstreams == 2 && split && tot <= cap && large.size() > 1) {
-        int64_t pre = 0, best = INT64_MAX;
-        for (size_t k = 0; k + 1 < large.size(); ++k) {
-            pre += 1ll << pl->slices[large[k]].logp;
-            const int64_t d = std::llabs(2 * pre - tot);
-            if (d < best) { best = d; cut = (int64_t)k + 1; }
-        }
-    } else if (pl->nstreams == 2 && split) {
-        cap = std::min(cap, std::max<int64_t>(1, (tot + 1) / 2));
-    }
-    int64_t acc = 0, wmax = 0;
-    for (size_t k = 0; k < large.size(); ++k) {
-        const int32_t si = large[k];
-        const int64_t P = 1ll << pl->slices[si].logp;
-        if (waves.empty() || (cut >= 0 ? (int64_t)k == cut : acc + P > cap)) { waves.emplace_back(); acc = 0; }
-        waves.back().push_back(si);
-        acc += P;
-        wmax = std::max(wmax, acc);
-    }
-    pl->nwaves = (int)waves.size();
-    const int nbuf = waves.size() > 1 ? pl->nstreams : 1;
-    // the tiny / small slices are independent of the waves: with two wave
-    // streams they get a third (latency-bound, they fill CUs beside both
-    // waves; splitting them over two streams measured slower on ResNet-50,
-    // 259-269 vs 273-276 GiB/s, profiles/r03_resnet50_row2_small2_ab.txt)
-    bool small_own = false;
-    if (nbuf == 2) {
-        for (Launch& l : common) l.stream = 2;
-        small_own = true;
-    } else if (pl->nstreams == 2 && !waves.empty()) {
-        // one wave (too few tiles to split): the small slices run beside it
-        // on the side stream
-        for (Launch& l : common) l.stream = 1;
-        small_own = true;
-    }
-    // on their own stream the small-slice launches are enqueued after the
-    // waves' (the critical path reaches the GPU first; each host enqueue costs
-    // microseconds); on a shared stream they go first as before
-    const bool small_last = !common.empty() && small_own;
-    pl->enc = small_last ? std::vector<Launch>{} : common;
-    pl->dec = small_last ? std::vector<Launch>{} : common;
-    pl->ws_floats = nbuf * wmax;
-    for (size_t w = 0; w < waves.size(); ++w) {
-        int64_t off = (int64_t)(w % nbuf) * wmax;
-        for (int32_t si : waves[w]) { pl->slices[si].ws_off = off; off += 1ll << pl->slices[si].logp; }
-    }
-    // decode row A reads 8-byte plane words when every plane row is 8-byte aligned
-    int a8 = 1;
-    for (int32_t si : large) a8 &= (pl->slices[si].pl_off % 8 == 0) && (pl->slices[si].pl_stride % 8 == 0);
-    // one wave with a k_col_multi launch and one small-set launch: fused
-    // (k_*_colm_set), everything on the caller's stream
-    bool fuse = false;
-    if (pl->fuse != 0 && waves.size() == 1 && common.size() == 1 && common[0].kind == K_SSET) {
-        std::set<int> hs;
-        for (int32_t si : waves[0]) {
-            const int r = pl->slices[si].logp - ofl::kRowLog;
-            if (r >= 1 && r <= kColMultiMax) hs.insert(r);
-        }
-        fuse = hs.size() >= 2;  // the condition for the k_col_multi launch below
-    }
-    pl->single = fuse;
-    if (fuse) {
-        pl->enc.clear();
-        pl->dec.clear();
-        for (Launch& l : common) l.stream = 0;
-    }
-    for (size_t w = 0; w < waves.size(); ++w) {
-        const std::vector<int32_t>& wl = waves[w];
-        const int s = (int)(w % nbuf);
-        int64_t rows = 0;
-        const int lo_l = add_list(wl);
-        const int rp = add_prefix(wl, ofl::kRowLog, rows);
-        // A 5-pass slice bigger than the wave size (its own wave): passes 1-2
-        // (row bits 0..14, column level 1 bits 15..15+m1-1) touch only a
-        // sub-block of 2^(15+m1) consecutive elements, and so do passes 4-5,
-        // so they run sub-wave by sub-wave (half a wave of nibble-even tiles
-        // and their pair partners 2^(p-18) tiles up), each sub-wave's two
-        // passes back to back while its intermediate sits in the MALL; the
-        // middle pass (column level 2 + D2) spans the slice and runs whole,
-        // writing the slice norm (it follows every row-A sub-wave).  Launches
-        // of one stream run in order, so no other synchronisation.
-        if (wl.size() == 1 && cap != INT64_MAX && pl->slices[wl[0]].logp - ofl::kRowLog >= 11) {
-            const int32_t si = wl[0];
-            const int p = pl->slices[si].logp, r = p - ofl::kRowLog, m1 = r / 2, m2 = r - m1;
-            const int64_t ntile = 1ll << r, sub = 1ll << m1, P = 1ll << (p - 18);
-            const int64_t cap_t = cap >> ofl::kRowLog;
-            const int64_t half = (cap_t / 2) / sub * sub;  // sub-wave size: the wave size
-            if (half >= sub && cap_t < ntile && ntile <= kRowTabMax && use_row2(2 * std::min(half, P), pl->ncu, pl->row2)) {
-                const bool pair = pl->pair != 0;
-                const int lo_c = add_list(wl);
-                int64_t tiles_all = 0;
-                const int tp = add_prefix(wl, ofl::kColLog, tiles_all);
-                struct SubWave { int tab_all, tab_pair; int64_t n_all, n_pair; };
-                std::vector<SubWave> sws;
-                for (int64_t reg = 0; reg < ntile; reg += 2 * P)
-                    for (int64_t c = 0; c < P; c += half) {
-                        const int64_t e = std::min(P, c + half);
-                        SubWave sw;
-                        sw.tab_all = (int)ints.size();
-                        for (int64_t h = 0; h < 2; ++h)
-                            for (int64_t t = reg + c + h * P; t < reg + e + h * P; ++t) {
-                                ints.push_back(si);
-                                ints.push_back((int32_t)(t << 3));
-                            }
-                        sw.n_all = 2 * (e - c);
-                        sw.tab_pair = (int)ints.size();
-                        for (int64_t t = reg + c; t < reg + e; ++t) {
-                            ints.push_back(si);
-                            ints.push_back((int32_t)(t << 3) | 1);
-                        }
-                        sw.n_pair = e - c;
-                        sws.push_back(sw);
-                    }
-                auto rowl = [&](Kind k, const SubWave& sw, bool paired) {
-                    Launch l{k, 0, 0, 0, lo_l, rp, 1, sw.n_all};
-                    l.expl = true;
-                    l.expl_tiles = sw.n_all;
-                    l.btab_off = sw.tab_all;
-                    if (paired) { l.ptab_off = sw.tab_pair; l.npair = (int)sw.n_pair; }
-                    l.stream = s;
-                    return l;
-                };
-                auto coll = [&](const SubWave& sw) {
-                    Launch l{K_COL, m1, ofl::kRowLog, 0, lo_c, tp, 1, sw.n_all};
-                    l.expl = true;
-                    l.expl_tiles = sw.n_all;
-                    l.btab_off = sw.tab_all;
-                    l.stream = s;
-                    return l;
-                };
-                for (int dir = 0; dir < 2; ++dir) {
-                    const bool enc = dir == 1;
-                    std::vector<Launch>& L = enc ? pl->enc : pl->dec;
-                    for (const SubWave& sw : sws) {
-                        Launch ra = rowl(K_ROWA, sw, enc && pair);
-                        if (!enc) ra.mid = a8;
-                        L.push_back(ra);
-                        L.push_back(coll(sw));
-                    }
-                    Launch mid{K_COL, m2, ofl::kRowLog + m1, 1, lo_c, tp, 1, tiles_all};
-                    mid.stream = s;
-                    mid.nt = m2 == 7;  // it streams its intermediate with nt loads and stores
-                    mid.nu = enc ? 1 : 0;  // after every row-A sub-wave: the slice norm
-                    L.push_back(mid);
-                    for (const SubWave& sw : sws) {
-                        L.push_back(coll(sw));
-                        L.push_back(rowl(K_ROWC, sw, !enc && pair));
-                    }
-                }
-                continue;
-            }
-        }
-        std::map<int, std::vector<int32_t>> byp;  // column launches grouped by p
-        for (int32_t si : wl) byp[pl->slices[si].logp].push_back(si);
-        std::vector<Launch> ce, cd;
-        // heights 1..kColMultiMax -> one k_col_multi
-        std::vector<std::pair<int, const std::vector<int32_t>*>> mg;
-        for (auto& kv : byp)
-            if (kv.first - ofl::kRowLog >= 1 && kv.first - ofl::kRowLog <= kColMultiMax) mg.push_back({kv.first - ofl::kRowLog, &kv.second});
-        if (mg.size() < 2) mg.clear();
-        if (!mg.empty()) {
-            const int gt = (int)ints.size();
-            ints.resize(ints.size() + ofl::kColGroup * mg.size());
-            int64_t blk = 0, mv = 0;
-            for (size_t g = 0; g < mg.size(); ++g) {
-                int64_t tiles = 0;
-                const int lo_c = add_list(*mg[g].second);
-                const int tp = add_prefix(*mg[g].second, ofl::kColLog, tiles);
-                int32_t* G = &ints[gt + ofl::kColGroup * g];
-                G[0] = mg[g].first;
-                G[1] = lo_c - gt;
-                G[2] = tp - gt;
-                G[3] = (int32_t)mg[g].second->size();
-                G[4] = (int32_t)blk;
-                blk += tiles;
-                for (int32_t si : *mg[g].second) mv += 8ll << pl->slices[si].logp;
-            }
-            Launch l{K_COLM, 0, ofl::kRowLog, 1, gt, -1, (int)mg.size(), blk};
-            l.stream = s;
-            l.bytes_moved = mv;
-            if (fuse) {  // the small-set groups ride in this launch (its first blocks)
-                l.kind = K_COLMSET;
-                l.sset_off = common[0].list_off;
-                l.sset_groups = common[0].count;
-                l.blocks += common[0].count;
-            }
-            cd.push_back(l);
-            l.nu = 1;  // encode: every group is a slice's first (only) column launch
-            ce.push_back(l);
-        }
-        for (auto& kv : byp) {
-            const int r = kv.first - ofl::kRowLog;
-            if (!mg.empty() && r >= 1 && r <= kColMultiMax) continue;  // in the k_col_multi launch
-            int64_t tiles = 0;
-            const int lo_c = add_list(kv.second);
-            const int tp = add_prefix(kv.second, ofl::kColLog, tiles);
-            const int cnt = (int)kv.second.size();
-            std::vector<Launch> seq;
-            if (r <= 10) {
-                seq.push_back({K_COL, r, ofl::kRowLog, 1, lo_c, tp, cnt, tiles});
-                if (r == 10)  // k_col6<10, true, 15>: interleaved ws (256-B segments in the middle pass)
-                    for (int32_t si : kv.second) pl->slices[si].perm = 1;
-            } else {  // two column levels; the middle launch carries D2
-                const int m1 = r / 2, m2 = r - m1;
-                seq.push_back({K_COL, m1, ofl::kRowLog, 0, lo_c, tp, cnt, tiles});
-                seq.push_back({K_COL, m2, ofl::kRowLog + m1, 1, lo_c, tp, cnt, tiles});
-                seq.push_back({K_COL, m1, ofl::kRowLog, 0, lo_c, tp, cnt, tiles});
-            }
-            for (Launch& l : seq) l.stream = s;
-            cd.insert(cd.end(), seq.begin(), seq.end());
-            seq[0].nu = 1;  // encode: the first column launch writes the slice norms
-            ce.insert(ce.end(), seq.begin(), seq.end());
-        }
-        Launch ra{K_ROWA, 0, 0, 0, lo_l, rp, (int)wl.size(), rows};
-        Launch rc{K_ROWC, 0, 0, 0, lo_l, rp, (int)wl.size(), rows};
-        ra.stream = rc.stream = s;
-        pl->enc.push_back(ra);
-        pl->enc.insert(pl->enc.end(), ce.begin(), ce.end());
-        pl->enc.push_back(rc);
-        ra.mid = a8;
-        pl->dec.push_back(ra);
-        pl->dec.insert(pl->dec.end(), cd.begin(), cd.end());
-        pl->dec.push_back(rc);
-    }
-    if (small_last && !fuse) {
-        pl->enc.insert(pl->enc.end(), common.begin(), common.end());
-        pl->dec.insert(pl->dec.end(), common.begin(), common.end());
-    }
-    // scales: one k_finalize per wave stream, after that stream's last row C,
-    // over the slices of its own waves.  A single finalize on the caller's
-    // stream would need a mid-call join, and a cross-queue wait costs the
-    // caller's queue ~10 us even when it is already satisfied (ResNet-50 trace)
-    for (int s = 0; s < nbuf; ++s) {
-        std::vector<int32_t> fl;
-        for (size_t w = s; w < waves.size(); w += nbuf) fl.insert(fl.end(), waves[w].begin(), waves[w].end());
-        if (fl.empty()) continue;
-        Launch f{K_FINAL, 0, 0, 0, add_list(fl), -1, (int)fl.size(), (int64_t)fl.size()};
-        f.stream = s;
-        pl->enc.push_back(f);
-    }
-    // column launches and the two-blocks-per-CU row launches: a per-block
-    // (per-tile) {slice, tile << 3 | group} table, so a block finds its tile
-    // with one load (a launch of few tiles per CU is latency-bound, and the
-    // prefix search is a chain of dependent loads); encode and decode share
-    // the table of the same list.  The persistent row kernels search their
-    // LDS copy of the prefix and take no table.
-    {
-        std::map<std::pair<int, int>, int> made;
-        auto table = [&](Launch& l) {
-            const auto key = std::make_pair(l.list_off, l.tstart_off);
-            auto it = made.find(key);
-            if (it != made.end()) { l.btab_off = it->second; return; }
-            std::vector<int32_t> t;
-            t.reserve(2 * (size_t)l.blocks);
-            auto add_group = [&](int list_off, int pre_off, int count, int g) {
-                for (int i = 0; i < count; ++i)
-                    for (int32_t k = 0; k < ints[pre_off + i + 1] - ints[pre_off + i]; ++k) {
-                        t.push_back(ints[list_off + i]);
-                        t.push_back((k << 3) | g);
-                    }
-            };
-            if (l.kind == K_COL || l.kind == K_ROWA || l.kind == K_ROWC) {
-                add_group(l.list_off, l.tstart_off, l.count, 0);
-            } else {  // K_COLM / K_COLMSET: l.count groups {M, list, tstart (relative), count, first block}
-                for (int g = 0; g < l.count; ++g) {
-                    const int32_t* G = &ints[l.list_off + ofl::kColGroup * g];
-                    add_group(l.list_off + G[1], l.list_off + G[2], G[3], g);
-                }
-            }
-            if ((int64_t)t.size() != 2 * (l.blocks - l.sset_groups)) return;  // inconsistent: keep the search
-            l.btab_off = (int)ints.size();
-            made[key] = l.btab_off;
-            ints.insert(ints.end(), t.begin(), t.end());
-        };
-        for (auto* L : {&pl->enc, &pl->dec})
-            for (Launch& l : *L)
-                if (!l.expl && (l.kind == K_COL || l.kind == K_COLM || l.kind == K_COLMSET ||
-                                ((l.kind == K_ROWA || l.kind == K_ROWC) && l.blocks <= kRowTabMax)))
-                    table(l);
-        // the sign-applying row launches (encode A, decode C): a paired table,
-        // one entry per tile of nibble-even position (its partner follows in
-        // the same block) and per tile of a slice below 2^18 (unpaired)
-        std::map<std::pair<int, int>, std::pair<int, int>> pmade;
-        auto ptable = [&](Launch& l) {
-            const auto key = std::make_pair(l.list_off, l.tstart_off);
-            auto it = pmade.find(key);
-            if (it != pmade.end()) { l.ptab_off = it->second.first; l.npair = it->second.second; return; }
-            std::vector<int32_t> t;
-            bool any = false;
-            for (int i = 0; i < l.count; ++i) {
-                const int32_t si = ints[l.list_off + i];
-                const int p = pl->slices[si].logp;
-                const int32_t nt = ints[l.tstart_off + i + 1] - ints[l.tstart_off + i];
-                for (int32_t k = 0; k < nt; ++k) {
-                    if (p >= 18 && ((k >> (p - 18)) & 1)) continue;  // a partner
-                    t.push_back(si);
-                    t.push_back((k << 3) | (p >= 18 ? 1 : 0));
-                    any = any || p >= 18;
-                }
-            }
-            if (!any) return;
-            l.ptab_off = (int)ints.size();
-            l.npair = (int)(t.size() / 2);
-            pmade[key] = {l.ptab_off, l.npair};
-            ints.insert(ints.end(), t.begin(), t.end());
-        };
-        for (Launch& l : pl->enc)
-            if (!l.expl && l.kind == K_ROWA && l.tstart_off >= 0 && l.blocks <= kRowTabMax) ptable(l);
-        for (Launch& l : pl->dec)
-            if (!l.expl && l.kind == K_ROWC && l.tstart_off >= 0 && l.blocks <= kRowTabMax) ptable(l);
-    }
-    // per-launch byte accounting (bench / DESIGN.md roofline)
-    const int64_t n_bits = pl->nbits;
-    for (int dir = 0; dir < 2; ++dir) {
-        const bool enc = dir == 1;
-        for (Launch& l : enc ? pl->enc : pl->dec) {
-            if (l.kind == K_COLM) continue;  // counted when built (its list is a group table)
-            int64_t mv = 0, al = 0;
-            if (l.kind == K_SSET || l.kind == K_COLMSET) {  // group table {P, offset, count}, then the slice ids
-                const int to = l.kind == K_SSET ? l.list_off : l.sset_off;
-                const int ng = l.kind == K_SSET ? l.count : l.sset_groups;
-                for (int g = 0; g < ng; ++g)
-                    for (int i = 0; i < ints[to + 3 * g + 2]; ++i) {
-                        const ofl::SliceDesc& D = pl->slices[ints[to + ints[to + 3 * g + 1] + i]];
-                        const int64_t pb = n_bits * (1ll << D.logp) / 8;
-                        mv += enc ? 4 * D.len + pb : pb + 4 * D.ylen;
-                    }
-                if (l.kind == K_SSET) l.bytes_moved = mv;
-                else l.bytes_moved += mv;  // + the column part, counted when built
-                l.bytes_alg = mv;
-                continue;
-            }
-            for (int i = 0; i < l.count; ++i) {
-                const ofl::SliceDesc& D = pl->slices[ints[l.list_off + i]];
-                const int64_t P = 1ll << D.logp, pb = n_bits * P / 8;
-                switch (l.kind) {
-                case K_TINY: case K_SMALL:
-                    mv += enc ? 4 * D.len + pb : pb + 4 * D.ylen; al = mv; break;
-                case K_ROWA:
-                    mv += enc ? 4 * D.len + 4 * P : pb + 4 * P; al += enc ? 4 * D.len : pb; break;
-                case K_ROWC:
-                    mv += enc ? 4 * P + pb : 4 * P + 4 * D.ylen; al += enc ? pb : 4 * D.ylen; break;
-                case K_COL: mv += 8 * P; break;
-                default: mv += 4 * (P >> ofl::kRowLog); break;
-                }
-                if (l.expl) {  // a sub-wave: its share of the slice's tiles
-                    mv = mv / (P >> ofl::kRowLog) * l.expl_tiles;
-                    al = al / (P >> ofl::kRowLog) * l.expl_tiles;
-                }
-            }
-            l.bytes_moved = mv;
-            l.bytes_alg = al;
-        }
-    }
 }
 
 int64_t env_i64(const char* name, int64_t dflt) {
     const char* s = getenv(name);
     return (s && *s) ? strtoll(s, nullptr, 10) : dflt;
+}
+
+// A plan's knobs are set before its first encode / decode, and every change
+// rebuilds the schedule.  range_err: empty, or why the value is refused.
+template <typename Assign>
+int set_knob(ofl_eden_plan_t pl, const char* what, const std::string& range_err, Assign assign) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    if (!range_err.empty()) return fail(OFL_EINVAL, range_err);
+    std::lock_guard<std::mutex> g(pl->mu);
+    if (pl->uploaded) return fail(OFL_EINVAL, std::string(what) + " must be set before the plan's first encode/decode");
+    assign(pl->p);
+    eden::build_schedule(pl->p, eden::kScheduleNcu);
+    return OFL_OK;
+}
+int set_mode(ofl_eden_plan_t pl, const char* what, const char* minus_one, int eden::Plan::*knob, int mode) {
+    const bool ok = mode >= -1 && mode <= 1;
+    return set_knob(pl, what, ok ? "" : std::string(what) + " mode must be -1 (" + minus_one + "), 0 or 1",
+                    [&](eden::Plan& p) { p.*knob = mode; });
+}
+
+// The one-call entry points keep a call's buffers in two blocks: encode reads
+// x | seeds and writes planes | scales; decode reads planes | scales | seeds.
+int encode_block(ofl_eden_plan_t pl, const void* in, size_t off_seeds, void* out, size_t off_scales, void* ws,
+                 size_t ws_bytes, void* stream) {
+    const char* i = static_cast<const char*>(in);
+    char* o = static_cast<char*>(out);
+    return ofl_eden_encode(pl, reinterpret_cast<const float*>(i), reinterpret_cast<const uint32_t*>(i + off_seeds),
+                           reinterpret_cast<uint8_t*>(o), reinterpret_cast<float*>(o + off_scales), ws, ws_bytes, stream);
+}
+int decode_block(ofl_eden_plan_t pl, const void* in, size_t off_scales, size_t off_seeds, void* y, void* ws,
+                 size_t ws_bytes, void* stream) {
+    const char* i = static_cast<const char*>(in);
+    return ofl_eden_decode(pl, reinterpret_cast<const uint8_t*>(i), reinterpret_cast<const uint32_t*>(i + off_seeds),
+                           reinterpret_cast<const float*>(i + off_scales), static_cast<float*>(y), ws, ws_bytes, stream);
+}
+// ofl_eden_encode_host_x, and with no x_host ofl_eden_encode_seeded, after their checks
+int encode_x(ofl_eden_plan_t pl, const void* x_host, size_t x_bytes, uint32_t seed, void* in_dev, size_t off_seeds,
+             void* out_dev, void* out_host, size_t out_bytes, size_t off_scales, void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* i = static_cast<char*>(in_dev);
+    if (x_host && x_bytes) HIP_TRY(hipMemcpyAsync(i, x_host, x_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(i + off_seeds), (int)seed, 1, st));
+    if (int rc = encode_block(pl, in_dev, off_seeds, out_dev, off_scales, ws, ws_bytes, stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(out_host, out_dev, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return OFL_OK;
 }
 
 }  // namespace
@@ -3196,23 +2530,7 @@ const char* ofl_version(void) { return "openfl_amd-codec 0.1 (gfx950)"; }
 const char* ofl_last_error(void) { return g_err.c_str(); }
 
 int ofl_eden_slice_plan(int64_t n, int64_t* P_out, int64_t* len_out, int max_slices) {
-    if (n <= 0) return 0;
-    int64_t rem = n;
-    int ns = 0;
-    while ((double)(high_po2(rem) - rem) / (double)n > 0.1) {
-        const int64_t low = low_po2(rem);
-        if (ns < max_slices) {
-            if (P_out) P_out[ns] = std::max<int64_t>(low, 8);
-            if (len_out) len_out[ns] = low;
-        }
-        ++ns;
-        rem -= low;
-    }
-    if (ns < max_slices) {
-        if (P_out) P_out[ns] = std::max<int64_t>(high_po2(rem), 8);
-        if (len_out) len_out[ns] = rem;
-    }
-    return ns + 1;
+    return eden::slice_plan(n, P_out, len_out, max_slices);
 }
 
 int ofl_eden_plan_create(int ntensors, const int64_t* numel, const int64_t* elem_offset,
@@ -3221,81 +2539,14 @@ int ofl_eden_plan_create(int ntensors, const int64_t* numel, const int64_t* elem
     if (!plan_out || ntensors < 0 || !numel || !elem_offset) return fail(OFL_EINVAL, "null argument");
     if (n_bits < 1 || n_bits > 8) return fail(OFL_EINVAL, "nbits value is not supported");
     auto* pl = new ofl_eden_plan();
-    pl->nbits = n_bits;
-    pl->ntensors = ntensors;
-    for (int t = 0; t < ntensors; ++t) pl->arena = std::max(pl->arena, elem_offset[t] + numel[t]);
-    int64_t dims_pos = 0;
-    // per-class slice lists
-    std::vector<int32_t>& tiny = pl->tiny;
-    std::vector<int32_t>* small = pl->small;
-    std::vector<int32_t>& large = pl->large;
-    for (int t = 0; t < ntensors; ++t) {
-        const int64_t n = numel[t];
-        std::vector<int64_t> Ps, Ls;  // padded sizes, valid input lengths
-        if (slice_dims) {
-            int64_t rem = n;
-            for (int k = 0; k < nslices[t]; ++k) {
-                const int64_t P = slice_dims[dims_pos + k];
-                Ps.push_back(P);
-                Ls.push_back(std::max<int64_t>(0, std::min<int64_t>(P, rem)));
-                rem -= Ls.back();
-            }
-            dims_pos += nslices[t];
-        } else {
-            int ns = ofl_eden_slice_plan(n, nullptr, nullptr, 0);
-            Ps.resize(ns);
-            Ls.resize(ns);
-            ofl_eden_slice_plan(n, Ps.data(), Ls.data(), ns);
-        }
-        int64_t Ptot = 0;
-        for (int64_t P : Ps) {
-            if (P < 8 || (P & (P - 1)) || P > (1ll << 29)) {
-                delete pl;
-                return fail(OFL_EINVAL, "slice size must be a power of two in [8, 2^29]");
-            }
-            Ptot += P;
-        }
-        pl->t_first.push_back((int32_t)pl->slices.size());
-        pl->t_nslices.push_back((int32_t)Ps.size());
-        const int64_t poff = (pl->planes_bytes + 255) & ~255ll;
-        pl->t_planes_off.push_back(poff);
-        pl->t_planes_bytes.push_back(Ptot / 8 * n_bits);
-        pl->planes_bytes = poff + Ptot / 8 * n_bits;
-        // Encode reads slice k from input offset sum(len_k') (Eden.compress
-        // advances by the valid length, :599-602); decode writes slice k's P
-        // outputs at sum(P_k') and truncates to total_dim (:650-657).  The two
-        // differ only for n < ~150 with a sub-8 non-final slice (reproduced).
-        int64_t off = 0, xoff = 0;
-        for (size_t k = 0; k < Ps.size(); ++k) {
-            const int64_t P = Ps[k];
-            ofl::SliceDesc D{};
-            D.x_off = elem_offset[t] + xoff;
-            D.len = Ls[k];
-            D.y_off = elem_offset[t] + off;
-            D.ylen = std::max<int64_t>(0, std::min<int64_t>(P, n - off));
-            D.pl_off = poff + off / 8;
-            D.pl_stride = Ptot / 8;
-            D.logp = ilog2(P);
-            D.tensor = t;
-            D.scale_idx = (int32_t)pl->slices.size();
-            const int si = (int)pl->slices.size();
-            if (D.logp <= 10) tiny.push_back(si);
-            else if (D.logp <= ofl::kRowLog) small[D.logp - 11].push_back(si);
-            else {
-                D.part_off = (int32_t)pl->part_floats;  // ws_off: build_schedule
-                pl->part_floats += P >> ofl::kRowLog;
-                large.push_back(si);
-            }
-            pl->slices.push_back(D);
-            off += P;
-            xoff += D.len;
-        }
+    if (const char* err = eden::layout(pl->p, ntensors, numel, elem_offset, nslices, slice_dims, n_bits)) {
+        delete pl;
+        return fail(OFL_EINVAL, err);
     }
-    pl->nlarge = (int64_t)large.size();
     // default schedule (tuning overrides: OFL_EDEN_WAVE_MIB, OFL_EDEN_STREAMS)
-    pl->wave_bytes = std::max<int64_t>(0, env_i64("OFL_EDEN_WAVE_MIB", kDefaultWaveMiB)) << 20;
-    pl->nstreams = (int)std::min<int64_t>(2, std::max<int64_t>(1, env_i64("OFL_EDEN_STREAMS", kDefaultStreams)));
-    build_schedule(pl);
+    pl->p.wave_bytes = std::max<int64_t>(0, env_i64("OFL_EDEN_WAVE_MIB", eden::kDefaultWaveMiB)) << 20;
+    pl->p.nstreams = (int)std::min<int64_t>(2, std::max<int64_t>(1, env_i64("OFL_EDEN_STREAMS", eden::kDefaultStreams)));
+    eden::build_schedule(pl->p, eden::kScheduleNcu);
     *plan_out = pl;
     return OFL_OK;
 }
@@ -3338,20 +2589,20 @@ static int ensure_device(ofl_eden_plan_t pl) {
     HIP_TRY(hipGetDevice(&pl->device));
     HIP_TRY(hipDeviceGetAttribute(&pl->ncu, hipDeviceAttributeMultiprocessorCount, pl->device));
     if (pl->ncu < 1) pl->ncu = 1;
-    if (!pl->slices.empty()) {
-        HIP_TRY(hipMalloc(&pl->d_slices, sizeof(ofl::SliceDesc) * pl->slices.size()));
-        HIP_TRY(hipMemcpy(pl->d_slices, pl->slices.data(), sizeof(ofl::SliceDesc) * pl->slices.size(), hipMemcpyHostToDevice));
+    if (!pl->p.slices.empty()) {
+        HIP_TRY(hipMalloc(&pl->d_slices, sizeof(ofl::SliceDesc) * pl->p.slices.size()));
+        HIP_TRY(hipMemcpy(pl->d_slices, pl->p.slices.data(), sizeof(ofl::SliceDesc) * pl->p.slices.size(), hipMemcpyHostToDevice));
     }
-    if (!pl->ints.empty()) {
-        HIP_TRY(hipMalloc(&pl->d_ints, sizeof(int32_t) * pl->ints.size()));
-        HIP_TRY(hipMemcpy(pl->d_ints, pl->ints.data(), sizeof(int32_t) * pl->ints.size(), hipMemcpyHostToDevice));
+    if (!pl->p.ints.empty()) {
+        HIP_TRY(hipMalloc(&pl->d_ints, sizeof(int32_t) * pl->p.ints.size()));
+        HIP_TRY(hipMemcpy(pl->d_ints, pl->p.ints.data(), sizeof(int32_t) * pl->p.ints.size(), hipMemcpyHostToDevice));
     }
     bool side = false;
-    for (const Launch& l : pl->enc) side |= l.stream != 0;
-    for (const Launch& l : pl->dec) side |= l.stream != 0;
+    for (const Launch& l : pl->p.enc) side |= l.stream != 0;
+    for (const Launch& l : pl->p.dec) side |= l.stream != 0;
     bool small = false;  // the small-slice stream
-    for (const Launch& l : pl->enc) small |= l.stream == 2;
-    for (const Launch& l : pl->dec) small |= l.stream == 2;
+    for (const Launch& l : pl->p.enc) small |= l.stream == 2;
+    for (const Launch& l : pl->p.dec) small |= l.stream == 2;
     if (side) {
         if (int rc = shared_side_streams(pl->device, small, pl->side, pl->side2)) return rc;
         HIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
@@ -3385,89 +2636,46 @@ void ofl_eden_plan_destroy(ofl_eden_plan_t pl) {
 }
 
 int ofl_eden_plan_set_schedule(ofl_eden_plan_t pl, int64_t wave_bytes, int streams) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
-    if (streams < 0 || streams > 2) return fail(OFL_EINVAL, "schedule: streams must be 1 or 2 (0 keeps)");
-    std::lock_guard<std::mutex> g(pl->mu);
-    if (pl->uploaded) return fail(OFL_EINVAL, "schedule must be set before the plan's first encode/decode");
-    if (wave_bytes >= 0) pl->wave_bytes = wave_bytes;
-    if (streams > 0) pl->nstreams = streams;
-    build_schedule(pl);
-    return OFL_OK;
+    const bool ok = streams >= 0 && streams <= 2;
+    return set_knob(pl, "schedule", ok ? "" : "schedule: streams must be 1 or 2 (0 keeps)", [&](eden::Plan& p) {
+        if (wave_bytes >= 0) p.wave_bytes = wave_bytes;
+        if (streams > 0) p.nstreams = streams;
+    });
 }
 
-int ofl_eden_plan_set_row2(ofl_eden_plan_t pl, int mode) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
-    if (mode < -1 || mode > 1) return fail(OFL_EINVAL, "row2 mode must be -1 (auto), 0 or 1");
-    std::lock_guard<std::mutex> g(pl->mu);
-    if (pl->uploaded) return fail(OFL_EINVAL, "row2 must be set before the plan's first encode/decode");
-    pl->row2 = mode;
-    build_schedule(pl);
-    return OFL_OK;
-}
-
-int ofl_eden_plan_set_pair(ofl_eden_plan_t pl, int mode) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
-    if (mode < -1 || mode > 1) return fail(OFL_EINVAL, "pair mode must be -1 (auto), 0 or 1");
-    std::lock_guard<std::mutex> g(pl->mu);
-    if (pl->uploaded) return fail(OFL_EINVAL, "pair must be set before the plan's first encode/decode");
-    pl->pair = mode;
-    build_schedule(pl);
-    return OFL_OK;
-}
-
-int ofl_eden_plan_set_sset(ofl_eden_plan_t pl, int mode) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
-    if (mode < -1 || mode > 1) return fail(OFL_EINVAL, "sset mode must be -1 (default), 0 or 1");
-    std::lock_guard<std::mutex> g(pl->mu);
-    if (pl->uploaded) return fail(OFL_EINVAL, "sset must be set before the plan's first encode/decode");
-    pl->sset = mode;
-    build_schedule(pl);
-    return OFL_OK;
-}
-
-int ofl_eden_plan_set_fuse(ofl_eden_plan_t pl, int mode) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
-    if (mode < -1 || mode > 1) return fail(OFL_EINVAL, "fuse mode must be -1 (default), 0 or 1");
-    std::lock_guard<std::mutex> g(pl->mu);
-    if (pl->uploaded) return fail(OFL_EINVAL, "fuse must be set before the plan's first encode/decode");
-    pl->fuse = mode;
-    build_schedule(pl);
-    return OFL_OK;
-}
+int ofl_eden_plan_set_row2(ofl_eden_plan_t pl, int mode) { return set_mode(pl, "row2", "auto", &eden::Plan::row2, mode); }
+int ofl_eden_plan_set_pair(ofl_eden_plan_t pl, int mode) { return set_mode(pl, "pair", "auto", &eden::Plan::pair, mode); }
+int ofl_eden_plan_set_sset(ofl_eden_plan_t pl, int mode) { return set_mode(pl, "sset", "default", &eden::Plan::sset, mode); }
+int ofl_eden_plan_set_fuse(ofl_eden_plan_t pl, int mode) { return set_mode(pl, "fuse", "default", &eden::Plan::fuse, mode); }
 
 int ofl_eden_plan_get_schedule(ofl_eden_plan_t pl, int64_t* wave_bytes, int* streams) {
     if (!pl) return fail(OFL_EINVAL, "null plan");
-    if (wave_bytes) *wave_bytes = pl->wave_bytes;
-    if (streams) *streams = pl->nstreams;
+    if (wave_bytes) *wave_bytes = pl->p.wave_bytes;
+    if (streams) *streams = pl->p.nstreams;
     return OFL_OK;
 }
 
-int ofl_eden_plan_num_waves(ofl_eden_plan_t pl) { return pl ? pl->nwaves : -1; }
+int ofl_eden_plan_num_waves(ofl_eden_plan_t pl) { return pl ? pl->p.nwaves : -1; }
 
-int64_t ofl_eden_plan_num_slices(ofl_eden_plan_t pl) { return pl ? (int64_t)pl->slices.size() : -1; }
-int64_t ofl_eden_plan_planes_bytes(ofl_eden_plan_t pl) { return pl ? pl->planes_bytes : -1; }
+int64_t ofl_eden_plan_num_slices(ofl_eden_plan_t pl) { return pl ? (int64_t)pl->p.slices.size() : -1; }
+int64_t ofl_eden_plan_planes_bytes(ofl_eden_plan_t pl) { return pl ? pl->p.planes_bytes : -1; }
 int64_t ofl_eden_plan_workspace_bytes(ofl_eden_plan_t pl) {
-    if (!pl) return -1;
-    // intermediates | partials | norms, each 256-B aligned
-    auto al = [](int64_t b) { return (b + 255) & ~255ll; };
-    // per-slice norms are indexed by slice id (all slices, not only large ones)
-    const int64_t nnu = (int64_t)pl->slices.size();
-    return al(pl->ws_floats * 4) + al(pl->part_floats * 4) + al(nnu * 4) + 256;
+    return pl ? eden::workspace_bytes(pl->p) : -1;
 }
 
 int ofl_eden_plan_tensor_info(ofl_eden_plan_t pl, int t, int64_t* planes_offset, int64_t* planes_bytes,
                               int32_t* first_slice, int32_t* nslices) {
-    if (!pl || t < 0 || t >= pl->ntensors) return fail(OFL_EINVAL, "tensor index out of range");
-    if (planes_offset) *planes_offset = pl->t_planes_off[t];
-    if (planes_bytes) *planes_bytes = pl->t_planes_bytes[t];
-    if (first_slice) *first_slice = pl->t_first[t];
-    if (nslices) *nslices = pl->t_nslices[t];
+    if (!pl || t < 0 || t >= pl->p.ntensors) return fail(OFL_EINVAL, "tensor index out of range");
+    if (planes_offset) *planes_offset = pl->p.t_planes_off[t];
+    if (planes_bytes) *planes_bytes = pl->p.t_planes_bytes[t];
+    if (first_slice) *first_slice = pl->p.t_first[t];
+    if (nslices) *nslices = pl->p.t_nslices[t];
     return OFL_OK;
 }
 
 int ofl_eden_plan_tensor_dims(ofl_eden_plan_t pl, int t, int64_t* dims_out) {
-    if (!pl || t < 0 || t >= pl->ntensors) return fail(OFL_EINVAL, "tensor index out of range");
-    for (int k = 0; k < pl->t_nslices[t]; ++k) dims_out[k] = 1ll << pl->slices[pl->t_first[t] + k].logp;
+    if (!pl || t < 0 || t >= pl->p.ntensors) return fail(OFL_EINVAL, "tensor index out of range");
+    for (int k = 0; k < pl->p.t_nslices[t]; ++k) dims_out[k] = 1ll << pl->p.slices[pl->p.t_first[t] + k].logp;
     return OFL_OK;
 }
 
@@ -3479,10 +2687,10 @@ static int prep_args(ofl_eden_plan_t pl, ofl::KArgs& a, void* ws, size_t ws_byte
     char* w = static_cast<char*>(ws);
     memset(&a, 0, sizeof(a));
     a.d = pl->d_slices;
-    a.nbits = pl->nbits;
+    a.nbits = pl->p.nbits;
     a.ws = reinterpret_cast<float*>(w);
-    a.part = reinterpret_cast<float*>(w + al(pl->ws_floats * 4));
-    a.nu = reinterpret_cast<float*>(w + al(pl->ws_floats * 4) + al(pl->part_floats * 4));
+    a.part = reinterpret_cast<float*>(w + al(pl->p.ws_floats * 4));
+    a.nu = reinterpret_cast<float*>(w + al(pl->p.ws_floats * 4) + al(pl->p.part_floats * 4));
     return OFL_OK;
 }
 
@@ -3543,17 +2751,12 @@ int ofl_eden_encode_host(ofl_eden_plan_t pl, const void* in_host, void* in_dev, 
                          void* out_dev, void* out_host, size_t out_bytes, size_t off_scales, void* ws, size_t ws_bytes,
                          void* stream) {
     if (!pl || !in_host || !in_dev || !out_dev || !out_host) return fail(OFL_EINVAL, "encode_host: null argument");
-    if (off_seeds + 4 * (size_t)pl->ntensors > in_bytes || off_seeds < 4 * (size_t)pl->arena ||
-        off_scales < (size_t)pl->planes_bytes || off_scales + 4 * pl->slices.size() > out_bytes)
+    if (off_seeds + 4 * (size_t)pl->p.ntensors > in_bytes || off_seeds < 4 * (size_t)pl->p.arena ||
+        off_scales < (size_t)pl->p.planes_bytes || off_scales + 4 * pl->p.slices.size() > out_bytes)
         return fail(OFL_EINVAL, "encode_host: block layout does not fit the plan");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemcpyAsync(in_dev, in_host, in_bytes, hipMemcpyHostToDevice, st));
-    char* o = static_cast<char*>(out_dev);
-    const char* i = static_cast<const char*>(in_dev);
-    if (int rc = ofl_eden_encode(pl, reinterpret_cast<const float*>(i), reinterpret_cast<const uint32_t*>(i + off_seeds),
-                                 reinterpret_cast<uint8_t*>(o), reinterpret_cast<float*>(o + off_scales), ws, ws_bytes,
-                                 stream))
-        return rc;
+    if (int rc = encode_block(pl, in_dev, off_seeds, out_dev, off_scales, ws, ws_bytes, stream)) return rc;
     HIP_TRY(hipMemcpyAsync(out_host, out_dev, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return OFL_OK;
@@ -3563,16 +2766,12 @@ int ofl_eden_decode_host(ofl_eden_plan_t pl, const void* in_host, void* in_dev, 
                          size_t off_seeds, void* out_dev, void* out_host, size_t out_bytes, void* ws, size_t ws_bytes,
                          void* stream) {
     if (!pl || !in_host || !in_dev || !out_dev || !out_host) return fail(OFL_EINVAL, "decode_host: null argument");
-    if (off_scales < (size_t)pl->planes_bytes || off_seeds < off_scales + 4 * pl->slices.size() ||
-        off_seeds + 4 * (size_t)pl->ntensors > in_bytes || out_bytes > 4 * (size_t)pl->arena)
+    if (off_scales < (size_t)pl->p.planes_bytes || off_seeds < off_scales + 4 * pl->p.slices.size() ||
+        off_seeds + 4 * (size_t)pl->p.ntensors > in_bytes || out_bytes > 4 * (size_t)pl->p.arena)
         return fail(OFL_EINVAL, "decode_host: block layout does not fit the plan");
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemcpyAsync(in_dev, in_host, in_bytes, hipMemcpyHostToDevice, st));
-    const char* i = static_cast<const char*>(in_dev);
-    if (int rc = ofl_eden_decode(pl, reinterpret_cast<const uint8_t*>(i), reinterpret_cast<const uint32_t*>(i + off_seeds),
-                                 reinterpret_cast<const float*>(i + off_scales), static_cast<float*>(out_dev), ws, ws_bytes,
-                                 stream))
-        return rc;
+    if (int rc = decode_block(pl, in_dev, off_scales, off_seeds, out_dev, ws, ws_bytes, stream)) return rc;
     if (out_bytes) HIP_TRY(hipMemcpyAsync(out_host, out_dev, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return OFL_OK;
@@ -3592,80 +2791,48 @@ static int mapped_ptr(void* h, void** d) {
 int ofl_eden_encode_mapped(ofl_eden_plan_t pl, const void* in_host, size_t off_seeds, void* out_host,
                            size_t off_scales, void* ws, size_t ws_bytes, void* stream) {
     if (!pl || !in_host || !out_host) return fail(OFL_EINVAL, "encode_mapped: null argument");
-    if (!pl->large.empty()) return fail(OFL_EINVAL, "encode_mapped: plans of tiny / small slices (<= 2^15) only");
-    if (off_seeds < 4 * (size_t)pl->arena || off_scales < (size_t)pl->planes_bytes)
+    if (!pl->p.large.empty()) return fail(OFL_EINVAL, "encode_mapped: plans of tiny / small slices (<= 2^15) only");
+    if (off_seeds < 4 * (size_t)pl->p.arena || off_scales < (size_t)pl->p.planes_bytes)
         return fail(OFL_EINVAL, "encode_mapped: block layout does not fit the plan");
     void *i = nullptr, *o = nullptr;
     if (int rc = mapped_ptr(const_cast<void*>(in_host), &i)) return rc;
     if (int rc = mapped_ptr(out_host, &o)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* oc = static_cast<char*>(o);
-    const char* ic = static_cast<const char*>(i);
-    if (int rc = ofl_eden_encode(pl, reinterpret_cast<const float*>(ic), reinterpret_cast<const uint32_t*>(ic + off_seeds),
-                                 reinterpret_cast<uint8_t*>(oc), reinterpret_cast<float*>(oc + off_scales), ws, ws_bytes,
-                                 stream))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = encode_block(pl, i, off_seeds, o, off_scales, ws, ws_bytes, stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return OFL_OK;
 }
 
 int ofl_eden_decode_mapped(ofl_eden_plan_t pl, const void* in_host, size_t off_scales, size_t off_seeds, void* y_host,
                            void* ws, size_t ws_bytes, void* stream) {
     if (!pl || !in_host || !y_host) return fail(OFL_EINVAL, "decode_mapped: null argument");
-    if (!pl->large.empty()) return fail(OFL_EINVAL, "decode_mapped: plans of tiny / small slices (<= 2^15) only");
-    if (off_scales < (size_t)pl->planes_bytes || off_seeds < off_scales + 4 * pl->slices.size())
+    if (!pl->p.large.empty()) return fail(OFL_EINVAL, "decode_mapped: plans of tiny / small slices (<= 2^15) only");
+    if (off_scales < (size_t)pl->p.planes_bytes || off_seeds < off_scales + 4 * pl->p.slices.size())
         return fail(OFL_EINVAL, "decode_mapped: block layout does not fit the plan");
     void *i = nullptr, *y = nullptr;
     if (int rc = mapped_ptr(const_cast<void*>(in_host), &i)) return rc;
     if (int rc = mapped_ptr(y_host, &y)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const char* ic = static_cast<const char*>(i);
-    if (int rc = ofl_eden_decode(pl, reinterpret_cast<const uint8_t*>(ic), reinterpret_cast<const uint32_t*>(ic + off_seeds),
-                                 reinterpret_cast<const float*>(ic + off_scales), static_cast<float*>(y), ws, ws_bytes,
-                                 stream))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = decode_block(pl, i, off_scales, off_seeds, y, ws, ws_bytes, stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return OFL_OK;
 }
 
 int ofl_eden_encode_seeded(ofl_eden_plan_t pl, void* in_dev, size_t off_seeds, uint32_t seed, void* out_dev,
                            void* out_host, size_t out_bytes, size_t off_scales, void* ws, size_t ws_bytes, void* stream) {
     if (!pl || !in_dev || !out_dev || !out_host) return fail(OFL_EINVAL, "encode_seeded: null argument");
-    if (pl->ntensors != 1 || off_seeds < 4 * (size_t)pl->arena || off_scales < (size_t)pl->planes_bytes ||
-        off_scales + 4 * pl->slices.size() > out_bytes)
+    if (pl->p.ntensors != 1 || off_seeds < 4 * (size_t)pl->p.arena || off_scales < (size_t)pl->p.planes_bytes ||
+        off_scales + 4 * pl->p.slices.size() > out_bytes)
         return fail(OFL_EINVAL, "encode_seeded: one-tensor plans; block layout does not fit the plan");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* i = static_cast<char*>(in_dev);
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(i + off_seeds), (int)seed, 1, st));
-    char* o = static_cast<char*>(out_dev);
-    if (int rc = ofl_eden_encode(pl, reinterpret_cast<const float*>(i), reinterpret_cast<const uint32_t*>(i + off_seeds),
-                                 reinterpret_cast<uint8_t*>(o), reinterpret_cast<float*>(o + off_scales), ws, ws_bytes,
-                                 stream))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out_host, out_dev, out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return OFL_OK;
+    return encode_x(pl, nullptr, 0, seed, in_dev, off_seeds, out_dev, out_host, out_bytes, off_scales, ws, ws_bytes, stream);
 }
 
 int ofl_eden_encode_host_x(ofl_eden_plan_t pl, const void* x_host, size_t x_bytes, uint32_t seed, void* in_dev,
                            size_t off_seeds, void* out_dev, void* out_host, size_t out_bytes, size_t off_scales,
                            void* ws, size_t ws_bytes, void* stream) {
     if (!pl || !in_dev || !out_dev || !out_host) return fail(OFL_EINVAL, "encode_host_x: null argument");
-    if (pl->ntensors != 1 || off_seeds < 4 * (size_t)pl->arena || (x_host && x_bytes > off_seeds) ||
-        off_scales < (size_t)pl->planes_bytes || off_scales + 4 * pl->slices.size() > out_bytes)
+    if (pl->p.ntensors != 1 || off_seeds < 4 * (size_t)pl->p.arena || (x_host && x_bytes > off_seeds) ||
+        off_scales < (size_t)pl->p.planes_bytes || off_scales + 4 * pl->p.slices.size() > out_bytes)
         return fail(OFL_EINVAL, "encode_host_x: block layout does not fit the plan");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* i = static_cast<char*>(in_dev);
-    if (x_host && x_bytes) HIP_TRY(hipMemcpyAsync(i, x_host, x_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(i + off_seeds), (int)seed, 1, st));
-    char* o = static_cast<char*>(out_dev);
-    if (int rc = ofl_eden_encode(pl, reinterpret_cast<const float*>(i), reinterpret_cast<const uint32_t*>(i + off_seeds),
-                                 reinterpret_cast<uint8_t*>(o), reinterpret_cast<float*>(o + off_scales), ws, ws_bytes,
-                                 stream))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out_host, out_dev, out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return OFL_OK;
+    return encode_x(pl, x_host, x_bytes, seed, in_dev, off_seeds, out_dev, out_host, out_bytes, off_scales, ws, ws_bytes, stream);
 }
 
 int ofl_eden_decode_host_x(ofl_eden_plan_t pl, const void* planes_host, size_t planes_bytes, const float* scales_host,
@@ -3673,22 +2840,20 @@ int ofl_eden_decode_host_x(ofl_eden_plan_t pl, const void* planes_host, size_t p
                            void* out_dev, void* y_host, size_t y_bytes, void* ws, size_t ws_bytes, void* stream) {
     if (!pl || !planes_host || !scales_host || !in_dev || !out_dev || !y_host)
         return fail(OFL_EINVAL, "decode_host_x: null argument");
-    if (pl->ntensors != 1 || planes_bytes != (size_t)pl->planes_bytes || nscales != (int)pl->slices.size() ||
-        off_scales < planes_bytes || off_seeds < off_scales + 4 * (size_t)nscales || y_bytes > 4 * (size_t)pl->arena)
+    if (pl->p.ntensors != 1 || planes_bytes != (size_t)pl->p.planes_bytes || nscales != (int)pl->p.slices.size() ||
+        off_scales < planes_bytes || off_seeds < off_scales + 4 * (size_t)nscales || y_bytes > 4 * (size_t)pl->p.arena)
         return fail(OFL_EINVAL, "decode_host_x: block layout does not fit the plan");
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* i = static_cast<char*>(in_dev);
     HIP_TRY(hipMemcpyAsync(i, planes_host, planes_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(i + off_scales, scales_host, 4 * (size_t)nscales, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(i + off_seeds), (int)seed, 1, st));
-    if (int rc = ofl_eden_decode(pl, reinterpret_cast<const uint8_t*>(i), reinterpret_cast<const uint32_t*>(i + off_seeds),
-                                 reinterpret_cast<const float*>(i + off_scales), static_cast<float*>(out_dev), ws, ws_bytes,
-                                 stream))
-        return rc;
+    if (int rc = decode_block(pl, in_dev, off_scales, off_seeds, out_dev, ws, ws_bytes, stream)) return rc;
     if (y_bytes) HIP_TRY(hipMemcpyAsync(y_host, out_dev, y_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return OFL_OK;
 }
+
 
 int ofl_copy_h2d_async(void* dst_dev, const void* src_host, size_t bytes, void* stream) {
     if (!bytes) return OFL_OK;
@@ -3807,35 +2972,40 @@ int ofl_eden_plan_profile(ofl_eden_plan_t pl, int enable) {
 
 int ofl_eden_plan_num_launches(ofl_eden_plan_t pl, int encode) {
     if (!pl) return fail(OFL_EINVAL, "null plan");
-    return (int)(encode ? pl->enc.size() : pl->dec.size());
+    return (int)(encode ? pl->p.enc.size() : pl->p.dec.size());
+}
+
+// What a launch of a plain encode / decode (no weighted average, aligned
+// planes) resolves to on the plan's device (256 CUs before its first use)
+static int resolve_plain(ofl_eden_plan_t pl, int encode, int idx, const Launch*& l, eden::Resolved& r) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    const std::vector<Launch>& L = encode ? pl->p.enc : pl->p.dec;
+    if (idx < 0 || idx >= (int)L.size()) return fail(OFL_EINVAL, "launch index out of range");
+    l = &L[idx];
+    if (const char* err = eden::resolve(pl->p, *l, encode != 0, pl->ncu, false, true, r)) return fail(OFL_EINVAL, err);
+    return OFL_OK;
 }
 
 int ofl_eden_plan_launch_info(ofl_eden_plan_t pl, int encode, int idx, char* name, int cap, int64_t* blocks,
                               int64_t* bytes_moved, int64_t* bytes_alg) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
-    const std::vector<Launch>& L = encode ? pl->enc : pl->dec;
-    if (idx < 0 || idx >= (int)L.size()) return fail(OFL_EINVAL, "launch index out of range");
-    if (name && cap > 0) {
-        const std::string s = launch_name(pl, L[idx], encode != 0);
-        snprintf(name, (size_t)cap, "%s", s.c_str());
-    }
-    if (blocks) *blocks = L[idx].blocks;
-    if (bytes_moved) *bytes_moved = L[idx].bytes_moved;
-    if (bytes_alg) *bytes_alg = L[idx].bytes_alg;
+    const Launch* l = nullptr;
+    eden::Resolved r;
+    if (int rc = resolve_plain(pl, encode, idx, l, r)) return rc;
+    if (name && cap > 0) snprintf(name, (size_t)cap, "%s", eden::kKernelName[r.id]);
+    if (blocks) *blocks = l->blocks;
+    if (bytes_moved) *bytes_moved = l->bytes_moved;
+    if (bytes_alg) *bytes_alg = l->bytes_alg;
     return OFL_OK;
 }
 
 int ofl_eden_plan_launch_detail(ofl_eden_plan_t pl, int encode, int idx, int32_t* explicit_tiles, int32_t* paired,
                                 int64_t* grid) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
-    const std::vector<Launch>& L = encode ? pl->enc : pl->dec;
-    if (idx < 0 || idx >= (int)L.size()) return fail(OFL_EINVAL, "launch index out of range");
-    const Launch& l = L[idx];
-    const bool row = l.kind == K_ROWA || l.kind == K_ROWC;
-    const RowChoice rc = row ? row_choice(pl, l, encode != 0, false) : RowChoice{false, l.expl, false, -1, 0, l.blocks};
-    if (explicit_tiles) *explicit_tiles = l.expl ? 1 : 0;
-    if (paired) *paired = rc.paired ? 1 : 0;
-    if (grid) *grid = rc.grid;
+    const Launch* l = nullptr;
+    eden::Resolved r;
+    if (int rc = resolve_plain(pl, encode, idx, l, r)) return rc;
+    if (explicit_tiles) *explicit_tiles = r.expl ? 1 : 0;
+    if (paired) *paired = r.paired ? 1 : 0;
+    if (grid) *grid = r.grid;
     return OFL_OK;
 }
 
@@ -3843,7 +3013,7 @@ int ofl_eden_plan_profile_collect(ofl_eden_plan_t pl, int encode, double* ms_sum
     if (!pl) return fail(OFL_EINVAL, "null plan");
     std::lock_guard<std::mutex> g(pl->mu);
     auto& calls = pl->prof_ev[encode ? 1 : 0];
-    const int nl = (int)(encode ? pl->enc.size() : pl->dec.size());
+    const int nl = (int)(encode ? pl->p.enc.size() : pl->p.dec.size());
     for (int i = 0; i < std::min(nl, max); ++i) ms_sum[i] = 0.0;
     for (auto& call : calls) {
         for (int i = 0; i < nl && i < max; ++i) {
