@@ -26,8 +26,8 @@ def float_to_int(np_array):
 
 class GZIPTransformer(Transformer):
     """float32 bytes -> gzip (lossless).  backend="device" (the pipelines'
-    default): the GPU gzip of rank arrays (lossy.gzip_ranks, TLZ in
-    csrc/deflate_kernels.hip); backend="host": gzip.compress at `level`
+    default): the GPU gzip of rank arrays (lossy.gzip_ranks, TLZ:
+    csrc/tlz_encode.h, driven by csrc/deflate_kernels.hip); backend="host": gzip.compress at `level`
     (large payloads as a multi-member stream compressed on host threads).
     Either way gzip.decompress reads the stream back to the same bytes."""
 

@@ -1,6 +1,6 @@
 """Member-indexed gzip streams written with zlib, for the inflate tests: every
 member carries the RFC 1952 extra subfield 'BC' (member size - 1), as the
-device gzip's members do (csrc/deflate_kernels.hip), but the deflate data is
+device gzip's members do (csrc/tlz_encode.h; the header fields: csrc/gz_format.h), but the deflate data is
 zlib's (stored / fixed / dynamic blocks, optional full flushes).  Test data
 generator only."""
 import struct

@@ -1,7 +1,7 @@
 """Designed deflate streams for the inflate tests (RFC 1951 / RFC 1952), in
 plain Python: a bit writer, canonical codes from explicit code lengths, the
 three block types from explicit token lists, the member headers the inflate
-kernels index ('BC' and the TLZ 'OZ' subfield of csrc/deflate_kernels.hip), a
+kernels index ('BC' and the TLZ 'OZ' subfield of csrc/gz_format.h), a
 ten-line LZ77 interpreter that gives the expected bytes without zlib, and a
 small reader of dynamic blocks that lists what an encoder wrote.  Test data
 only: no device code.

@@ -1,4 +1,4 @@
-"""TLZ gzip / inflate check on the GPU (csrc/deflate_kernels.hip, gz::tlz):
+"""TLZ gzip / inflate check on the GPU (csrc/tlz_encode.h and tlz_decode.h, gz::tlz):
 round trips through gzip.decompress and the device inflate, the ratio
 against gzip -9, and the kernel times on the 1 GiB KC rank set.
 

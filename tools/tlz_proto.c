@@ -1,4 +1,4 @@
-// tools/tlz_proto.c -- CPU simulation of the TLZ encoder (csrc/deflate_kernels.hip, gz::tlz) used to
+// tools/tlz_proto.c -- CPU simulation of the TLZ encoder (csrc/tlz_encode.h, gz::tlz) used to
 // choose its parameters: member / segment size, window, chain candidates (NC), frontier entries (F),
 // DP segment (S) and sweeps (SW), the cost model (ENTROPY=1: -log2 frequencies; else Huffman lengths),
 // minimum match (minl), unrolled DP lengths (UNR=k).  Exact DEFLATE bit counting, header included.
