@@ -146,6 +146,9 @@ int ofl_eden_plan_tensor_dims(ofl_eden_plan_t plan, int t, int64_t* dims_out);
  * Decode: planes_arena + scales -> y_arena (only the numel[t] elements of each
  *        tensor are written).
  * ws: DEVICE workspace of at least ofl_eden_plan_workspace_bytes() bytes.
+ * planes_arena may have any byte alignment in every encode and decode call
+ *        (outputs do not depend on it), and decode multiplies by the scale
+ *        last, float32(scale * value), for every float32 scale.
  * Everything is enqueued on `stream`; nothing synchronises. */
 int ofl_eden_encode(ofl_eden_plan_t plan, const float* x_arena, const uint32_t* seeds,
                     uint8_t* planes_arena, float* scales, void* ws, size_t ws_bytes,

@@ -518,6 +518,19 @@ DEVI void load_planes(const uint8_t* plane0, uint32_t e, int64_t stride, int nbi
 
 DEVI float pow2i(int e) { return __int_as_float((127 + e) << 23); }  // 2^e, |e| < 127
 
+// The row passes' last multiply: a decoded value is float32(sc * (v * 2^-k)).
+// 2^-k is exact, so v * (sc * 2^-k) rounds like that while sc * 2^-k is a
+// normal number: the factor to apply.  Below 2^-100 (zero, or a subnormal
+// scale from the wire: the product would lose the scale's low bits; k <= 15)
+// v takes 2^-k here and the factor is sc itself.  sc is block-uniform.
+DEVI float fold_scale(float sc, int k, float (&v)[64]) {
+    const float m = pow2i(-k);
+    if (fabsf(sc) >= pow2i(-100)) return sc * m;
+#pragma unroll
+    for (int r = 0; r < 64; ++r) v[r] *= m;
+    return sc;
+}
+
 // Hide a value from the optimiser so per-register addresses are recomputed
 // (cheap ALU) instead of being kept live across a whole pass (32 VGPRs).
 
@@ -1422,10 +1435,9 @@ __global__ __launch_bounds__(kRowNT) void k_dec_rowC(KArgs a) {
         stages<RS::L2, RS::F1b>(v);
         exchange<RS::L2, RS::L1>(v, s, tid);
         stages<RS::L1, RS::F1a>(v);
-        // scale folded into the 2^-k normalisation: 2^-k is exact, so
-        // v * (sc * 2^-k) rounds like (v * 2^-k) * sc (normal range)
-        const float sc = sldf(a.scales_in, D.scale_idx);
-        apply_signs_direct<RS::L1>(v, tile << kRowLog, base1, D.logp, b1, sc * pow2i(-((D.logp + 1) / 2)));
+        // scale folded into the 2^-k normalisation (fold_scale)
+        const float mul = fold_scale(sldf(a.scales_in, D.scale_idx), (D.logp + 1) / 2, v);
+        apply_signs_direct<RS::L1>(v, tile << kRowLog, base1, D.logp, b1, mul);
         store_y(a, D, tile, base1, v);
         if (!more) break;
         t = tn; si = sn; tile = tln;
@@ -2259,8 +2271,7 @@ __global__ __launch_bounds__(kRowNT, 4) void k_dec_rowC2(KArgs a) {
         stages<R::B3, R::H3>(v);
         exchange_half_pad<R::B3, R::B4, 10>(v, s, tid);
         stages<R::B4, R::H4>(v);
-        const float sc = sldf(a.scales_in, D.scale_idx);
-        const float mul = sc * pow2i(-((D.logp + 1) / 2));
+        const float mul = fold_scale(sldf(a.scales_in, D.scale_idx), (D.logp + 1) / 2, v);
         if (pair) apply_signs_pair<R::B4>(v, tile << kRowLog, base4, D.logp, b1, mul, 1u + h, stash);
         else apply_signs_grouped<R::B4>(v, tile << kRowLog, base4, D.logp, b1, mul);
         store_y_l<R::B4>(a, D, tile, base4, v);

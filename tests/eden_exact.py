@@ -58,9 +58,29 @@ def fwht(v):
     return v.div_(math.sqrt(P))
 
 
+_packed = {}
+_packed_bytes = 0
+PACKED_CACHE_BYTES = 1 << 27
+
+
+def packed_signs(P, seed):
+    """oracle.eden.rand_signs(P, seed), kept (the oracle hashes on one thread:
+    0.5 s at 2^26) while the kept arrays stay below PACKED_CACHE_BYTES."""
+    global _packed_bytes
+    key = (int(P), int(seed))
+    if key not in _packed:
+        if _packed_bytes + (P + 7) // 8 > PACKED_CACHE_BYTES:
+            _packed.clear()
+            _packed_bytes = 0
+        _packed[key] = O.rand_signs(P, seed)
+        _packed[key].setflags(write=False)
+        _packed_bytes += _packed[key].nbytes
+    return _packed[key]
+
+
 def signs(P, seed, dtype, device):
     """rand_diag(P, seed) as a +-1 tensor, from oracle.eden.rand_signs."""
-    packed = torch.from_numpy(O.rand_signs(P, seed)).to(device)
+    packed = torch.tensor(packed_signs(P, seed), device=device)  # a copy: the kept array is read-only
     bit = (packed[:, None] >> torch.arange(8, device=device, dtype=torch.uint8)[None, :]) & 1
     return bit.reshape(-1)[:P].to(dtype).mul_(2).sub_(1)
 
