@@ -414,6 +414,22 @@ int ofl_lut_decode_batch(int ntensors, const float* in_arena, const int64_t* off
 const char* ofl_agg_last_error(void);
 int ofl_wavg_delta(int ncollab, const float* const* xs, const double* weights, double wsum, const float* base,
                    int64_t n, double* agg_out, double* delta64_out, float* delta32_out, void* stream);
+/* The same average one collaborator at a time (nothing in the sum needs them
+ * together): ofl_wavg_delta's sequence of roundings per element, so the same
+ * bits, with one float64 sums arena resident instead of every collaborator.
+ * ofl_wavg_accumulate  first != 0: sums[i] = (double)x[i] * w (the product
+ *                 is stored, not added to zero: a -0.0 product stays -0.0, as
+ *                 in ofl_wavg_delta's first launch);
+ *                 otherwise sums[i] = sums[i] + (double)x[i] * w.  Call in the
+ *                 collaborators' order.  Reads 4 + 8, writes 8 bytes/element.
+ * ofl_wavg_finish sums[i] = sums[i] / wsum in place (the average), then the
+ *                 delta as ofl_wavg_delta writes it: delta64_out float64 (not
+ *                 the sums themselves), delta32_out rounded to float32; base
+ *                 and either output may be NULL.  Reads 8 + 4, writes 8 + 4.
+ *                 Single-element tensors: ofl_wavg_delta_points afterwards. */
+int ofl_wavg_accumulate(const float* x, double w, int first, int64_t n, double* sums, void* stream);
+int ofl_wavg_finish(double* sums, double wsum, const float* base, int64_t n, double* delta64_out, float* delta32_out,
+                    void* stream);
 /* ofl_wavg_delta_seeds  the Eden seeds of a round end without a host round
  *                 trip: the float64 delta on the listed ranges (packed_dev,
  *                 total doubles; single_dev[r] != 0: a single-element tensor,

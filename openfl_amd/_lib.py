@@ -30,7 +30,7 @@ EXPORTS = (
     "ofl_lut_decode_batch_workspace_bytes", "ofl_lut_decode_batch",
     "ofl_sparsify_topk_batch_workspace_bytes", "ofl_sparsify_topk_batch",
     "ofl_ternary_ranks_batch_workspace_bytes", "ofl_ternary_ranks_batch",
-    "ofl_agg_last_error", "ofl_wavg_delta", "ofl_wavg_delta_seeds", "ofl_py_hash_doubles",
+    "ofl_agg_last_error", "ofl_wavg_delta", "ofl_wavg_accumulate", "ofl_wavg_finish", "ofl_wavg_delta_seeds", "ofl_py_hash_doubles",
     "ofl_wavg_points_workspace_bytes", "ofl_wavg_delta_points", "ofl_apply_delta",
     "ofl_apply_delta_ranges", "ofl_wavg_delta32_ranges", "ofl_sub_f32_f64",
     "ofl_median_delta", "ofl_gmedian_workspace_bytes", "ofl_gmedian_delta", "ofl_agg_delta_seeds",
@@ -158,6 +158,10 @@ def _bind(L):
     L.ofl_agg_last_error.restype = ctypes.c_char_p
     L.ofl_wavg_delta.argtypes = [i32, vp, vp, ctypes.c_double, vp, i64, vp, vp, vp, vp]
     L.ofl_wavg_delta.restype = i32
+    L.ofl_wavg_accumulate.argtypes = [vp, ctypes.c_double, i32, i64, vp, vp]
+    L.ofl_wavg_accumulate.restype = i32
+    L.ofl_wavg_finish.argtypes = [vp, ctypes.c_double, vp, i64, vp, vp, vp]
+    L.ofl_wavg_finish.restype = i32
     L.ofl_wavg_delta_seeds.argtypes = [i32, vp, vp, ctypes.c_double, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.ofl_wavg_delta_seeds.restype = i32
     L.ofl_py_hash_doubles.argtypes = [vp, i32, vp, vp]

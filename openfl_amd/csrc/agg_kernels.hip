@@ -214,6 +214,89 @@ __global__ __launch_bounds__(kNT) void k_wavg_delta(WavgArgs a, int vec) {
     quads_then_tail(a.n, vec, [&](int64_t i) { wavg_quad(a, i); }, [&](int64_t i) { wavg_elem(a, i); });
 }
 
+// The streaming form of the same average: one collaborator per launch into a
+// float64 sums arena, then one pass that divides and takes the delta.  The
+// sequence of roundings per element is k_wavg_delta's: the first product is
+// stored as it is (a -0.0 product stays -0.0, as wavg_sum keeps it; adding it
+// to +0.0 would not),
+// every later one is added to the running sum, the last pass divides by wsum.
+// k_wavg_accumulate reads 4 + 8 and writes 8 bytes per element (first: no
+// read of the sums), k_wavg_finish reads 8 + 4 and writes 8 + 4 (+ 8 with
+// delta64).
+struct AccArgs {
+    const float* x;
+    double w;
+    int first;     // store the product instead of adding it
+    double* sums;
+    int64_t n;
+};
+
+__device__ __forceinline__ void acc_elem(const AccArgs& a, int64_t i) {
+#pragma clang fp contract(off)
+    const double p = (double)a.x[i] * a.w;
+    a.sums[i] = a.first ? p : a.sums[i] + p;
+}
+
+// 4 consecutive elements per thread: one 16-B load of x, the sums as two
+// 16-B pairs each way
+__device__ __forceinline__ void acc_quad(const AccArgs& a, int64_t i) {
+#pragma clang fp contract(off)
+    const float4 v = *reinterpret_cast<const float4*>(a.x + i);
+    double2* s2 = reinterpret_cast<double2*>(a.sums + i);
+    double2 lo, hi;
+    lo.x = (double)v.x * a.w; lo.y = (double)v.y * a.w;
+    hi.x = (double)v.z * a.w; hi.y = (double)v.w * a.w;
+    if (!a.first) {
+        const double2 p = s2[0], q = s2[1];
+        lo.x = p.x + lo.x; lo.y = p.y + lo.y;
+        hi.x = q.x + hi.x; hi.y = q.y + hi.y;
+    }
+    s2[0] = lo;
+    s2[1] = hi;
+}
+
+__global__ __launch_bounds__(kNT) void k_wavg_accumulate(AccArgs a, int vec) {
+    quads_then_tail(a.n, vec, [&](int64_t i) { acc_quad(a, i); }, [&](int64_t i) { acc_elem(a, i); });
+}
+
+struct FinishArgs {
+    double wsum;
+    DeltaOut o;    // o.agg: the sums, divided in place
+    int64_t n;
+};
+
+__device__ __forceinline__ void finish_elem(const FinishArgs& a, int64_t i) {
+#pragma clang fp contract(off)
+    a.o.put(i, a.o.agg[i] / a.wsum);
+}
+
+__device__ __forceinline__ void finish_quad(const FinishArgs& a, int64_t i) {
+#pragma clang fp contract(off)
+    double2* s2 = reinterpret_cast<double2*>(a.o.agg + i);
+    double2 lo = s2[0], hi = s2[1];
+    lo.x = lo.x / a.wsum; lo.y = lo.y / a.wsum;
+    hi.x = hi.x / a.wsum; hi.y = hi.y / a.wsum;
+    s2[0] = lo;
+    s2[1] = hi;
+    if (!a.o.delta64 && !a.o.delta32) return;
+    if (a.o.base) {  // DeltaOut::delta on the four
+        const float4 b = *reinterpret_cast<const float4*>(a.o.base + i);
+        lo.x = lo.x - (double)b.x; lo.y = lo.y - (double)b.y;
+        hi.x = hi.x - (double)b.z; hi.y = hi.y - (double)b.w;
+    }
+    if (a.o.delta64) {
+        double2* d2 = reinterpret_cast<double2*>(a.o.delta64 + i);
+        d2[0] = lo;
+        d2[1] = hi;
+    }
+    if (a.o.delta32)
+        *reinterpret_cast<float4*>(a.o.delta32 + i) = make_float4((float)lo.x, (float)lo.y, (float)hi.x, (float)hi.y);
+}
+
+__global__ __launch_bounds__(kNT) void k_wavg_finish(FinishArgs a, int vec) {
+    quads_then_tail(a.n, vec, [&](int64_t i) { finish_quad(a, i); }, [&](int64_t i) { finish_elem(a, i); });
+}
+
 // Single-element tensors: NumPy reduces a (C, 1) stack as a 1-D array, i.e.
 // np_pairwise of all C products.
 struct PointArgs {
@@ -459,6 +542,33 @@ int ofl_wavg_delta(int ncollab, const float* const* xs, const double* weights, d
         hipLaunchKernelGGL(agg::k_wavg_delta, dim3(g), dim3(agg::kNT), 0, st, a, vec);
         AHIP(hipGetLastError());
     }
+    return OFL_OK;
+}
+
+int ofl_wavg_accumulate(const float* x, double w, int first, int64_t n, double* sums, void* stream) {
+    if (n < 0 || (n && (!x || !sums))) return afail(OFL_EINVAL, "wavg_accumulate: bad arguments");
+    if (n == 0) return OFL_OK;
+    agg::AccArgs a{x, w, first ? 1 : 0, sums, n};
+    const int vec = aligned16(&x, 1, sums);
+    hipLaunchKernelGGL(agg::k_wavg_accumulate, dim3(grid_for(n, 4)), dim3(agg::kNT), 0,
+                       static_cast<hipStream_t>(stream), a, vec);
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_wavg_finish(double* sums, double wsum, const float* base, int64_t n, double* delta64_out, float* delta32_out,
+                    void* stream) {
+    if (n < 0 || (n && !sums)) return afail(OFL_EINVAL, "wavg_finish: bad arguments");
+    if (delta64_out && delta64_out == sums) return afail(OFL_EINVAL, "wavg_finish: delta64_out must not be the sums");
+    if (n == 0) return OFL_OK;
+    agg::FinishArgs a{};
+    a.wsum = wsum;
+    a.o = {base, sums, delta64_out, delta32_out};
+    a.n = n;
+    const int vec = aligned16(&base, 0, base, sums, delta64_out, delta32_out);
+    hipLaunchKernelGGL(agg::k_wavg_finish, dim3(grid_for(n, 4)), dim3(agg::kNT), 0, static_cast<hipStream_t>(stream),
+                       a, vec);
+    AHIP(hipGetLastError());
     return OFL_OK;
 }
 
