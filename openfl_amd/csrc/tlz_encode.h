@@ -131,7 +131,7 @@ struct EncArgs {
 };
 constexpr int kEncPhases = 16;
 
-// k-means label of one value (k_bkm_label's rule, lossy_kernels.hip)
+// k-means label of one value (k_bkm_label's rule, lossy_kmeans.h)
 DEVI float lab_rank(float v, const float* m, const float* r) {
     float o = r[0];
 #pragma unroll

@@ -1,10 +1,12 @@
 """Device ops behind the KC / SKC / STC pipelines (libofl_codec.so lossy ABI).
 
 Each function takes/returns PyTorch-ROCm device tensors and host scalars; the
-heavy O(n) work runs in openfl_amd/csrc/lossy_kernels.hip.  Reference
-semantics are cited per function (paths relative to /root/reference).
+heavy O(n) work runs in the kernels of openfl_amd/csrc/lossy_kernels.hip (its
+lossy_*.h headers).  Reference semantics are cited per function (paths
+relative to /root/reference).
 """
 import ctypes
+import functools
 import gzip
 import os
 import threading
@@ -25,8 +27,6 @@ def _on_device(fn):
     """Run fn with its first device-tensor argument's GPU current: per-device
     setup inside the library (CRC tables, kernel attributes, CU counts) keys
     on hipGetDevice(), and the launches go to that tensor's stream."""
-    import functools
-
     @functools.wraps(fn)
     def wrap(*args, **kwargs):
         for a in list(args) + list(kwargs.values()):
@@ -37,18 +37,8 @@ def _on_device(fn):
     return wrap
 
 
-def _ws(device, n):
-    need = int(_lib.lib().ofl_lossy_workspace_bytes(int(n)))
-    bufs = getattr(_tls, "ws", None)
-    if bufs is None:
-        bufs = _tls.ws = {}
-    b = bufs.get(str(device))
-    if b is None or b.numel() < need:
-        b = bufs[str(device)] = torch.empty(need, dtype=torch.uint8, device=device)
-    return b
-
-
 def _ws_bytes(device, need):
+    """This thread's workspace on `device`, grown to at least `need` bytes."""
     bufs = getattr(_tls, "ws", None)
     if bufs is None:
         bufs = _tls.ws = {}
@@ -56,6 +46,16 @@ def _ws_bytes(device, need):
     if b is None or b.numel() < need:
         b = bufs[str(device)] = torch.empty(need, dtype=torch.uint8, device=device)
     return b
+
+
+def _ws(device, n):
+    """The workspace of a one-tensor call on n elements."""
+    return _ws_bytes(device, int(_lib.lib().ofl_lossy_workspace_bytes(int(n))))
+
+
+def _arena_index(offsets, numels):
+    """(T, offsets, numels) of a batched call: contiguous int64 arrays."""
+    return len(numels), np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(numels, np.int64)
 
 
 def _stream(device):
@@ -179,9 +179,7 @@ def kmeans_batch(x_arena, offsets, numels, k=6, n_init=6, seed=0, max_exact=8, v
     -> (centres [T, k], counts [T, k], inertia [T], uniq: list of arrays)."""
     _check_dev(x_arena)
     L = _lib.lib()
-    T = len(numels)
-    off = np.ascontiguousarray(offsets, np.int64)
-    num = np.ascontiguousarray(numels, np.int64)
+    T, off, num = _arena_index(offsets, numels)
     need = int(L.ofl_kmeans1d_batch_workspace_bytes(T, num.ctypes.data))
     ws = _ws_bytes(x_arena.device, need)
     c = np.zeros((T, k), np.float64)
@@ -258,9 +256,7 @@ def sparsify_topk_batch(x_arena, offsets, numels, ks, sparse_out):
     _check_dev(x_arena)
     _check_dev(sparse_out)
     L = _lib.lib()
-    T = len(numels)
-    off = np.ascontiguousarray(offsets, np.int64)
-    num = np.ascontiguousarray(numels, np.int64)
+    T, off, num = _arena_index(offsets, numels)
     kk = np.ascontiguousarray(ks, np.int64)
     ws = _ws_bytes(x_arena.device, int(L.ofl_sparsify_topk_batch_workspace_bytes(T, num.ctypes.data)))
     kmin = np.zeros(T, np.float32)
@@ -283,9 +279,7 @@ def ternary_ranks_batch(sparse_arena, offsets, numels, ranks3, out_arena):
     _check_dev(sparse_arena)
     _check_dev(out_arena)
     L = _lib.lib()
-    T = len(numels)
-    off = np.ascontiguousarray(offsets, np.int64)
-    num = np.ascontiguousarray(numels, np.int64)
+    T, off, num = _arena_index(offsets, numels)
     r3 = np.ascontiguousarray(ranks3, np.float32).reshape(T, 3)
     ws = _ws_bytes(sparse_arena.device, int(L.ofl_ternary_ranks_batch_workspace_bytes(T)))
     _lib.check_lossy(L.ofl_ternary_ranks_batch(T, sparse_arena.data_ptr(), off.ctypes.data, num.ctypes.data,
@@ -337,7 +331,7 @@ def lut_decode_batch(ranks_arena, offsets, numels, maps, out_arena):
     _check_dev(ranks_arena)
     _check_dev(out_arena)
     L = _lib.lib()
-    T = len(numels)
+    T, off, num = _arena_index(offsets, numels)
     mk = max([len(m) for m in maps] + [1])
     keys = np.zeros((T, mk), np.float32)
     vals = np.zeros((T, mk), np.float32)
@@ -346,8 +340,6 @@ def lut_decode_batch(ranks_arena, offsets, numels, maps, out_arena):
         nk[t] = len(m)
         for j, (k, v) in enumerate(m.items()):
             keys[t, j], vals[t, j] = float(k), float(v)
-    off = np.ascontiguousarray(offsets, np.int64)
-    num = np.ascontiguousarray(numels, np.int64)
     ws = _ws_bytes(ranks_arena.device, int(L.ofl_lut_decode_batch_workspace_bytes(T, mk)))
     _lib.check_lossy(L.ofl_lut_decode_batch(T, ranks_arena.data_ptr(), off.ctypes.data, num.ctypes.data,
                                             nk.ctypes.data, keys.ctypes.data, vals.ctypes.data, mk,

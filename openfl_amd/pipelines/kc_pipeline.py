@@ -1,7 +1,7 @@
 """KCPipeline on MI355X: drop-in for openfl/pipelines/kc_pipeline.py.
 
 KmeansTransformer (k-means quantisation, :16-114) + GZIPTransformer (:117-156).
-k-means runs on the GPU (openfl_amd/csrc/lossy_kernels.hip); sklearn's
+k-means runs on the GPU (openfl_amd/csrc/lossy_kmeans.h); sklearn's
 KMeans RNG cannot be reproduced, so centres match the reference statistically
 (inertia within 1 %, tests/test_gpu_lossy.py) while the metadata schema, rank
 semantics and wire format are the reference's.  Decoding a reference payload

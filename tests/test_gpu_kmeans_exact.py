@@ -1,4 +1,4 @@
-"""The device 1-D k-means (k_bkm_* and k_km_label, lossy_kernels.hip) held to
+"""The device 1-D k-means (k_bkm_* in csrc/lossy_kmeans.h, k_km_label in lossy_single.h) held to
 its contract exactly: fed with the centres a fit returns, tests/kmeans_ref.py
 (float64 numpy) says what every rank, count, unique value and the inertia of
 that fit must be.  test_kmeans_ref_cpu.py shows on the host that the same

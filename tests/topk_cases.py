@@ -1,4 +1,4 @@
-"""Designed inputs of the batched radix top-k (k_btk_* in csrc/lossy_kernels.hip)
+"""Designed inputs of the batched radix top-k (k_btk_* in csrc/lossy_topk.h)
 and the numpy reference they are compared with.  numpy only, no tests: the
 designs are checked on the host by test_topk_cases_cpu.py and run on the device
 by test_gpu_topk_designed.py.
