@@ -618,6 +618,25 @@ int ofl_gzip_ranks_to(const float* x, int64_t n, uint8_t* out, size_t out_cap, u
 int ofl_gzip_label_to(const float* x, int64_t n, const ofl_label_rec* label_tab, int ntensors, uint8_t* out,
                       size_t out_cap, uint8_t* host_dst, size_t host_cap, int nthreads, size_t* out_len, void* ws,
                       size_t ws_bytes, void* stream);
+/* ofl_gzip_ranks of every tensor of an arena in one call: tensor t is
+ * ranks_arena[offsets[t], offsets[t] + numels[t]) (DEVICE float32, element
+ * positions of any alignment; offsets, numels: HOST, numels[t] >= 1 -- the
+ * caller leaves empty tensors out), and its stream -- byte for byte what
+ * ofl_gzip_ranks of that slice gives -- is out[tensor_end[t - 1],
+ * tensor_end[t]) (from 0 for t = 0; tensor_end: HOST, ntensors entries).  The
+ * members of all tensors are encoded in launches of up to 512 driven by a
+ * member table, longest members first, packed back to back and copied to the
+ * host as in the pinned path of ofl_gzip_ranks; out must be mapped pinned
+ * host memory (else OFL_EINVAL) of out_cap bytes: OFL_ESPACE if the streams
+ * do not fit (ofl_gzip_ranks_batch_bound always does).  A value that is not
+ * an integer 0..31 -> OFL_EINVAL, nothing usable in out.  ws: device,
+ * ofl_gzip_ranks_batch_workspace_bytes (0, like the bound, for a list the
+ * call refuses: no tensors, an empty tensor, more than 2^31 - 1 members).
+ * Synchronous, one stream synchronisation. */
+size_t ofl_gzip_ranks_batch_workspace_bytes(int ntensors, const int64_t* numels);
+size_t ofl_gzip_ranks_batch_bound(int ntensors, const int64_t* numels);
+int ofl_gzip_ranks_batch(int ntensors, const float* ranks_arena, const int64_t* offsets, const int64_t* numels,
+                         uint8_t* out, size_t out_cap, uint64_t* tensor_end, void* ws, size_t ws_bytes, void* stream);
 /* GZIPTransformer.backward (kc_pipeline.py:152-156: gzip.decompress) for a
  * stream whose members all carry a size field ('OZ', or BGZF's 'BC'):
  * members are located from their headers and inflated (zlib) on nthreads host

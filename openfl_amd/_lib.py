@@ -36,6 +36,7 @@ EXPORTS = (
     "ofl_median_delta", "ofl_gmedian_workspace_bytes", "ofl_gmedian_delta", "ofl_agg_delta_seeds",
     "ofl_adaptive_step",
     "ofl_gzip_last_error", "ofl_gzip_ranks_workspace_bytes", "ofl_gzip_ranks_bound", "ofl_gzip_ranks", "ofl_gzip_ranks_to", "ofl_gzip_label_to", "ofl_side_stream",
+    "ofl_gzip_ranks_batch_workspace_bytes", "ofl_gzip_ranks_batch_bound", "ofl_gzip_ranks_batch",
     "ofl_gunzip_members", "ofl_gzip_member_index", "ofl_inflate_members", "ofl_inflate_tlz_workspace_bytes",
     "ofl_inflate_tlz", "ofl_inflate_tlz_async", "ofl_inflate_tlz_wait", "ofl_inflate_tlz_launch", "ofl_inflate_tlz_launch_lut", "ofl_inflate_tlz_check", "ofl_gzip_profile", "ofl_gzip_profile_collect",
 )
@@ -200,6 +201,12 @@ def _bind(L):
     L.ofl_gzip_ranks_to.restype = i32
     L.ofl_gzip_label_to.argtypes = [vp, i64, vp, i32, vp, sz, vp, sz, i32, vp, vp, sz, vp]
     L.ofl_gzip_label_to.restype = i32
+    L.ofl_gzip_ranks_batch_workspace_bytes.argtypes = [i32, vp]
+    L.ofl_gzip_ranks_batch_workspace_bytes.restype = sz
+    L.ofl_gzip_ranks_batch_bound.argtypes = [i32, vp]
+    L.ofl_gzip_ranks_batch_bound.restype = sz
+    L.ofl_gzip_ranks_batch.argtypes = [i32, vp, vp, vp, vp, sz, vp, vp, sz, vp]
+    L.ofl_gzip_ranks_batch.restype = i32
     L.ofl_side_stream.argtypes = [i32, ctypes.POINTER(ctypes.c_void_p)]
     L.ofl_side_stream.restype = i32
     L.ofl_gunzip_members.argtypes = [vp, sz, vp, sz, vp, i32]

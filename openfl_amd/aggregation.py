@@ -636,9 +636,9 @@ class _LossyTail:
         if payloads and nd:
             if self.kind == "stc":
                 ranks = lossy.ternary_ranks_batch(x, self.off, self.num, r3, re._empty_arena())
+            enc = self.gz.forward_device_batch(ranks, self.off, self.num)  # one encode for the whole update
             for t, i in enumerate(self.dev):
-                o, n = int(self.off[t]), int(self.num[t])
-                payload, gz_md = self.gz.forward_device(ranks[o:o + n])
+                payload, gz_md = enc[t]
                 result[i] = (payload, self._metadata(i, maps[t], gz_md))
         return out, result, seeds
 

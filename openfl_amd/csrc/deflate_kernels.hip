@@ -188,7 +188,10 @@ hipError_t gz_device_setup() {
         gz::crc_matrices(m);
         hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(gz::c_adv), m, sizeof(m));
         if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)gz::tlz::k_tlz_encode, hipFuncAttributeMaxDynamicSharedMemorySize,
+            e = hipFuncSetAttribute((const void*)gz::tlz::k_tlz_encode<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)sizeof(gz::tlz::EncSmem));
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)gz::tlz::k_tlz_encode<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)sizeof(gz::tlz::EncSmem));
         if (e == hipSuccess)
             e = hipFuncSetAttribute((const void*)gz::k_inflate_members<65536, false, false>,
@@ -197,8 +200,10 @@ hipError_t gz_device_setup() {
     });
 }
 
-// what the two paths of gzip_ranks_impl share: the call's arguments and the
-// workspace's regions (gz::GzRanksWs) as pointers
+// what the two paths of gzip_ranks_impl and the batched call share: the call's
+// arguments and the workspace's regions (gz::GzRanksWs) as pointers.  The
+// members are those of one stream x[0, n), or (tab non-null) the ones a member
+// table names (gz::TlzBatchPlan)
 struct GzRanksJob {
     const float* x;
     int64_t n;
@@ -219,13 +224,33 @@ struct GzRanksJob {
     uint8_t* stage[2];
     int aligned;      // x is 16-byte aligned
     uint64_t* d_ph;   // diagnostics (OFL_GZ_PHASES), else null
+    // the batched call (device; else null): the member table, the launch
+    // order, every tensor's end offset, and the host array that receives them
+    const gz::tlz::MemberRec* tab = nullptr;
+    const int32_t* order = nullptr;
+    uint64_t* tend = nullptr;
+    uint64_t* tend_host = nullptr;
+    int ntensors = 0;
     // members [c0, c0 + nb) into slots[b], sizes[b]
     void encode(int64_t c0, int nb, int b) const {
-        gz::tlz::EncArgs a{x, n, c0, slots[b], ops, sizes[b], bad, (uint32_t)L.slot, (uint32_t)L.ops_stride, aligned,
-                           c0 == 0 ? d_ph : nullptr, lab, lab ? lab_n : 0};
+        const gz::tlz::EncArgs a{x, n, c0, slots[b], ops, sizes[b], bad, (uint32_t)L.slot, (uint32_t)L.ops_stride, aligned,
+                                 c0 == 0 ? d_ph : nullptr, lab, lab ? lab_n : 0};
         gzprof_begin(st);
-        hipLaunchKernelGGL(gz::tlz::k_tlz_encode, dim3(nb), dim3(gz::tlz::kNT), sizeof(gz::tlz::EncSmem), st, a);
-        gzprof_end(st, "tlz::k_tlz_encode");
+        if (tab) {
+            gz::tlz::EncTabArgs t;
+            static_cast<gz::tlz::EncArgs&>(t) = a;
+            t.tab = tab;
+            t.order = order;
+            hipLaunchKernelGGL(gz::tlz::k_tlz_encode<true>, dim3(nb), dim3(gz::tlz::kNT), sizeof(gz::tlz::EncSmem), st, t);
+        } else {
+            hipLaunchKernelGGL(gz::tlz::k_tlz_encode<false>, dim3(nb), dim3(gz::tlz::kNT), sizeof(gz::tlz::EncSmem), st, a);
+        }
+        gzprof_end(st, tab ? "tlz::k_tlz_encode<table>" : "tlz::k_tlz_encode");
+    }
+    // behind the scan of members [c0, c0 + nb): the end offsets of the tensors whose last member is among them
+    void tensor_ends(int64_t c0, int nb, int b) const {
+        hipLaunchKernelGGL(gz::tlz::k_tlz_tensor_end, dim3(1), dim3(gz::tlz::kBatch), 0, st, tab, c0, nb, L.members, off[b],
+                           tend);
     }
 };
 
@@ -361,6 +386,7 @@ int gzip_ranks_pinned(const GzRanksJob& J, uint8_t* dout, size_t* total) {
         hipLaunchKernelGGL(gz::k_gzip_scan, dim3(1), dim3(1024), 0, st, J.sizes[b], nb, J.off[b], J.running,
                            (uint64_t)J.out_cap, J.bad);
         gzprof_end(st, "k_gzip_scan");
+        if (J.tab) J.tensor_ends(c0, nb, b);
         GZHIP(hipMemcpyAsync(hinfo + 2 * b, J.off[b], 8, hipMemcpyDeviceToHost, st));
         GZHIP(hipMemcpyAsync(hinfo + 2 * b + 1, J.off[b] + nb, 8, hipMemcpyDeviceToHost, st));
         GZHIP(hipEventRecord(ev.scan[b], st));
@@ -397,6 +423,7 @@ int gzip_ranks_pinned(const GzRanksJob& J, uint8_t* dout, size_t* total) {
     int badh = 0;
     GZHIP(hipMemcpyAsync(&tot, J.running, 8, hipMemcpyDeviceToHost, st));
     GZHIP(hipMemcpyAsync(&badh, J.bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (J.tend_host) GZHIP(hipMemcpyAsync(J.tend_host, J.tend, 8 * (size_t)J.ntensors, hipMemcpyDeviceToHost, st));
     GZHIP(hipStreamSynchronize(st));
     ev.drained = true;  // st waited for everything sd ran
     if (badh & 1) return gzfail(OFL_EINVAL, "gzip ranks: values must be float32 integers 0..31");
@@ -438,6 +465,28 @@ int gzip_ranks_pageable(const GzRanksJob& J, size_t* total_out) {
     return OFL_OK;
 }
 
+// the workspace's regions as the job's pointers
+void job_regions(GzRanksJob& J, const gz::GzRanksWs& W, char* w) {
+    for (int i = 0; i < 2; ++i) {
+        J.slots[i] = reinterpret_cast<uint8_t*>(w + W.slots[i]);
+        J.sizes[i] = reinterpret_cast<uint32_t*>(w + W.sizes[i]);
+        J.off[i] = reinterpret_cast<uint64_t*>(w + W.off[i]);
+        J.stage[i] = reinterpret_cast<uint8_t*>(w + W.stage[i]);
+    }
+    J.ops = reinterpret_cast<uint32_t*>(w + W.ops);
+    J.running = reinterpret_cast<uint64_t*>(w + W.running);
+    J.bad = reinterpret_cast<int*>(w + W.bad);
+}
+// the device address of mapped pinned host memory, null for any other pointer
+uint8_t* mapped_address(const void* out) {
+    uint8_t* dout = nullptr;
+    hipPointerAttribute_t pa;
+    if (hipPointerGetAttributes(&pa, out) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer)
+        dout = static_cast<uint8_t*>(pa.devicePointer);
+    (void)hipGetLastError();  // a pageable pointer is not an error here
+    return dout;
+}
+
 // host_dst (optional): a pageable buffer of host_cap bytes that receives the
 // stream too, each batch copied on nthreads host threads while the next batch
 // encodes (ofl_gzip_ranks_to)
@@ -453,26 +502,12 @@ int gzip_ranks_impl(const float* x, int64_t n, const ofl_label_rec* lab, int lab
     if (!ws || ws_bytes < W.end) return gzfail(OFL_ESPACE, "gzip ranks: workspace too small");
     GZHIP(gz_device_setup());
     GzRanksJob J{x, n, lab, lab_n, out, out_cap, host_dst, nthreads, static_cast<hipStream_t>(stream), W.L};
-    for (int i = 0; i < 2; ++i) {
-        J.slots[i] = reinterpret_cast<uint8_t*>(w + W.slots[i]);
-        J.sizes[i] = reinterpret_cast<uint32_t*>(w + W.sizes[i]);
-        J.off[i] = reinterpret_cast<uint64_t*>(w + W.off[i]);
-        J.stage[i] = reinterpret_cast<uint8_t*>(w + W.stage[i]);
-    }
-    J.ops = reinterpret_cast<uint32_t*>(w + W.ops);
-    J.running = reinterpret_cast<uint64_t*>(w + W.running);
-    J.bad = reinterpret_cast<int*>(w + W.bad);
+    job_regions(J, W, w);
     GZHIP(hipMemsetAsync(J.bad, 0, sizeof(int), J.st));
     // out is mapped pinned host memory (e.g. torch pin_memory): the pack
     // kernel's output goes straight towards it and the batches run back to
     // back with one synchronisation at the end; otherwise one D2H per batch
-    uint8_t* dout = nullptr;
-    {
-        hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, out) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer)
-            dout = static_cast<uint8_t*>(pa.devicePointer);
-        (void)hipGetLastError();  // a pageable pointer is not an error here
-    }
+    uint8_t* const dout = mapped_address(out);
     J.aligned = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
     // diagnostics: OFL_GZ_PHASES=1 prints block 0's phase times (10 ns ticks,
     // summed over its segments; [11] = Jacobi rounds) of the first launch
@@ -497,6 +532,45 @@ int gzip_ranks_impl(const float* x, int64_t n, const ofl_label_rec* lab, int lab
     }
     *out_len = total;
     return OFL_OK;
+}
+
+// ofl_gzip_ranks_batch: the pinned pipeline over the members of a table.
+// The table and the order are built on the host and copied into ws; the
+// vectors outlive the copies, since every return below the first enqueue
+// waits for the stream (Drain, or the pipeline's own end)
+int gzip_ranks_batch_impl(int ntensors, const float* x, const int64_t* offsets, const int64_t* numels, uint8_t* out,
+                          size_t out_cap, uint64_t* tensor_end, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !offsets || !numels || !out || !tensor_end) return gzfail(OFL_EINVAL, "gzip ranks batch: null argument");
+    gz::TlzBatchPlan P;
+    if (!gz::tlz_batch_plan(ntensors, offsets, numels, P))
+        return gzfail(OFL_EINVAL, "gzip ranks batch: no tensors, an empty tensor, a negative offset or too many members");
+    char* w = static_cast<char*>(ws);
+    const gz::GzBatchWs W = gz::gzip_batch_ws(P.L, ntensors, reinterpret_cast<uintptr_t>(w));
+    if (!ws || ws_bytes < W.end) return gzfail(OFL_ESPACE, "gzip ranks batch: workspace too small");
+    uint8_t* const dout = mapped_address(out);
+    if (!dout) return gzfail(OFL_EINVAL, "gzip ranks batch: out must be mapped pinned host memory");
+    GZHIP(gz_device_setup());
+    GzRanksJob J{x, 0, nullptr, 0, out, out_cap, nullptr, 1, static_cast<hipStream_t>(stream), P.L};
+    job_regions(J, W.R, w);
+    J.aligned = 0;
+    J.d_ph = nullptr;
+    J.tab = reinterpret_cast<const gz::tlz::MemberRec*>(w + W.tab);
+    J.order = reinterpret_cast<const int32_t*>(w + W.order);
+    J.tend = reinterpret_cast<uint64_t*>(w + W.tend);
+    J.tend_host = tensor_end;
+    J.ntensors = ntensors;
+    struct Drain {
+        hipStream_t st;
+        bool armed = true;
+        ~Drain() { if (armed) (void)hipStreamSynchronize(st); }
+    } drain{J.st};
+    GZHIP(hipMemcpyAsync(w + W.tab, P.rec.data(), sizeof(gz::tlz::MemberRec) * P.rec.size(), hipMemcpyHostToDevice, J.st));
+    GZHIP(hipMemcpyAsync(w + W.order, P.order.data(), 4 * P.order.size(), hipMemcpyHostToDevice, J.st));
+    GZHIP(hipMemsetAsync(J.bad, 0, sizeof(int), J.st));
+    size_t total = 0;
+    const int rc = gzip_ranks_pinned(J, dout, &total);
+    drain.armed = rc != OFL_OK;  // a call that succeeds has waited once, at the pipeline's end
+    return rc;
 }
 }  // namespace
 
@@ -526,6 +600,23 @@ int ofl_gzip_label_to(const float* x, int64_t n, const ofl_label_rec* label_tab,
     if (!label_tab) return gzfail(OFL_EINVAL, "gzip label: null label_tab");
     return gzip_ranks_impl(x, n, label_tab, ntensors, out, out_cap, host_dst, host_cap, std::max(1, nthreads), out_len,
                            ws, ws_bytes, stream);
+}
+
+size_t ofl_gzip_ranks_batch_workspace_bytes(int ntensors, const int64_t* numels) {
+    gz::TlzLayout L;
+    size_t bound = 0;
+    return gz::tlz_batch_layout(ntensors, numels, L, bound) ? gz::gzip_batch_ws(L, ntensors, 0).end : 0;
+}
+
+size_t ofl_gzip_ranks_batch_bound(int ntensors, const int64_t* numels) {
+    gz::TlzLayout L;
+    size_t bound = 0;
+    return gz::tlz_batch_layout(ntensors, numels, L, bound) ? bound : 0;
+}
+
+int ofl_gzip_ranks_batch(int ntensors, const float* ranks_arena, const int64_t* offsets, const int64_t* numels,
+                         uint8_t* out, size_t out_cap, uint64_t* tensor_end, void* ws, size_t ws_bytes, void* stream) {
+    return gzip_ranks_batch_impl(ntensors, ranks_arena, offsets, numels, out, out_cap, tensor_end, ws, ws_bytes, stream);
 }
 
 // Host inflate of a member-indexed gzip stream (every member carries the

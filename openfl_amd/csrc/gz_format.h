@@ -57,6 +57,12 @@ constexpr int kSlotPerTok = 6;                     // worst-case member bytes pe
 constexpr int kSlotPad = 8192;                     // + headers
 constexpr int kBatch = 512;                        // members per launch
 
+// a record of the batched encoder's member table (ofl_gzip_ranks_batch): the
+// member's first value as an arena element position, its 1..kMemTok values,
+// and the tensor whose stream it belongs to
+struct MemberRec { int64_t start; int32_t count; int32_t tensor; };
+static_assert(sizeof(MemberRec) == 16, "one 16-byte load per record");
+
 // the 'OZ' subfield of a TLZ member, offsets from its SI1; it is the only
 // subfield, so the segment table ends where the deflate data starts
 constexpr int kVersion = 1;

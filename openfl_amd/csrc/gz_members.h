@@ -2,9 +2,11 @@
 // free of HIP so that it can be built and checked alone
 // (tests/gz_members_check.cpp): the parser of a member-indexed stream's
 // headers -- untrusted bytes off the wire --, the CRC-32 advance matrices, and
-// the layouts of the encoder's and the inflate's workspaces.
+// the layouts of the encoder's and the inflate's workspaces, and the batched
+// encoder's member table and launch order.
 #pragma once
 #include <algorithm>
+#include <climits>
 #include <cstddef>
 #include <cstdint>
 #include <thread>
@@ -205,9 +207,9 @@ struct GzRanksWs {
     size_t stage[2];   // [stage] a batch's D2H staging
     size_t end;
 };
-inline GzRanksWs gzip_ranks_ws(int64_t n, uintptr_t base) {
+inline GzRanksWs gzip_ranks_ws(const TlzLayout& L, uintptr_t base) {
     GzRanksWs W;
-    W.L = tlz_layout(n);
+    W.L = L;
     const size_t B = (size_t)W.L.batch;
     size_t at = 0, counted = 0;
     auto take = [&](size_t bytes, size_t align, bool count) {
@@ -225,6 +227,112 @@ inline GzRanksWs gzip_ranks_ws(int64_t n, uintptr_t base) {
     W.bad = take(4, 4, false);
     for (size_t& s : W.stage) s = take(W.L.stage, 256, true);
     W.end = counted + kWsSmall;
+    return W;
+}
+inline GzRanksWs gzip_ranks_ws(int64_t n, uintptr_t base) { return gzip_ranks_ws(tlz_layout(n), base); }
+
+// ---- the batched encoder (ofl_gzip_ranks_batch): many streams in one arena --
+// Tensor t's numels[t] >= 1 values give ceil(numels[t] / kMemTok) consecutive
+// members, all but the last full; members in tensor order.  A launch takes
+// kBatch consecutive members of that table.
+inline size_t tlz_slot_bytes(int64_t count) { return ((size_t)count * tlz::kSlotPerTok + tlz::kSlotPad + 255) & ~(size_t)255; }
+
+// the sizes alone, from the element counts: the layout (slot and ops_stride
+// from the largest member, stage from the launch with the most values) and
+// the largest packed stream (every member at its own worst case).  false for
+// an empty list, a tensor without values or more members than an int32 holds
+inline bool tlz_batch_layout(int64_t ntensors, const int64_t* numels, TlzLayout& L, size_t& bound) {
+    using namespace tlz;
+    L = TlzLayout{0, 0, 0, 0, 0};
+    bound = 0;
+    if (ntensors < 1 || ntensors > INT32_MAX || !numels) return false;
+    int64_t members = 0, per = 0;
+    for (int64_t t = 0; t < ntensors; ++t) {
+        if (numels[t] < 1 || numels[t] > (int64_t)INT32_MAX * kMemTok) return false;
+        members += (numels[t] + kMemTok - 1) / kMemTok;
+        if (members > INT32_MAX) return false;
+        per = std::max(per, std::min<int64_t>(numels[t], kMemTok));
+    }
+    // the launches, without the table: runs of full members, then a tensor's last one
+    int64_t fill = 0, vals = 0, most = 0;
+    auto add = [&](int64_t nmem, int64_t count) {
+        bound += (size_t)nmem * tlz_slot_bytes(count);
+        while (nmem > 0) {
+            const int64_t take = std::min<int64_t>(nmem, kBatch - fill);
+            fill += take;
+            vals += take * count;
+            nmem -= take;
+            most = std::max(most, vals);
+            if (fill == kBatch) fill = vals = 0;
+        }
+    };
+    for (int64_t t = 0; t < ntensors; ++t) {
+        add(numels[t] / kMemTok, kMemTok);
+        if (numels[t] % kMemTok) add(1, numels[t] % kMemTok);
+    }
+    L.members = members;
+    L.batch = std::min<int64_t>(members, kBatch);
+    L.slot = tlz_slot_bytes(per);
+    L.ops_stride = ((size_t)per + 63) & ~(size_t)63;
+    L.stage = ((size_t)most + 255) & ~(size_t)255;
+    return true;
+}
+
+// the member table and the launch order: order[c0 + j], for the launch whose
+// first member is c0, is the member (relative to c0) that block j encodes --
+// members by count descending (ties in table order), so that the long members
+// start first and the short ones fill in behind them
+struct TlzBatchPlan {
+    TlzLayout L;
+    size_t bound;
+    std::vector<tlz::MemberRec> rec;
+    std::vector<int32_t> order;
+};
+inline bool tlz_batch_plan(int64_t ntensors, const int64_t* offsets, const int64_t* numels, TlzBatchPlan& P) {
+    using namespace tlz;
+    P.rec.clear();
+    P.order.clear();
+    if (!offsets || !tlz_batch_layout(ntensors, numels, P.L, P.bound)) return false;
+    P.rec.reserve((size_t)P.L.members);
+    for (int64_t t = 0; t < ntensors; ++t) {
+        if (offsets[t] < 0) return false;
+        for (int64_t at = 0; at < numels[t]; at += kMemTok)
+            P.rec.push_back({offsets[t] + at, (int32_t)std::min<int64_t>(kMemTok, numels[t] - at), (int32_t)t});
+    }
+    P.order.resize(P.rec.size());
+    for (size_t c0 = 0; c0 < P.rec.size(); c0 += kBatch) {
+        const size_t nb = std::min<size_t>(kBatch, P.rec.size() - c0);
+        int32_t* o = P.order.data() + c0;
+        for (size_t j = 0; j < nb; ++j) o[j] = (int32_t)j;
+        std::stable_sort(o, o + nb, [&](int32_t a, int32_t b) { return P.rec[c0 + a].count > P.rec[c0 + b].count; });
+    }
+    return true;
+}
+
+// the ofl_gzip_ranks_batch workspace: the single stream's regions for the
+// batch layout, then the member table, the launch order and the tensors' end
+// offsets.  end does not depend on base (the three align-ups skip < 16 + 4 + 8)
+struct GzBatchWs {
+    GzRanksWs R;
+    size_t tab;      // [members] MemberRec
+    size_t order;    // [members] int32
+    size_t tend;     // [ntensors] uint64
+    size_t end;
+};
+inline GzBatchWs gzip_batch_ws(const TlzLayout& L, int64_t ntensors, uintptr_t base) {
+    GzBatchWs W;
+    W.R = gzip_ranks_ws(L, base);
+    size_t at = W.R.end;
+    auto take = [&](size_t bytes, size_t align) {
+        at += (align - (base + at) % align) % align;
+        const size_t o = at;
+        at += bytes;
+        return o;
+    };
+    W.tab = take(sizeof(tlz::MemberRec) * (size_t)L.members, 16);
+    W.order = take(4 * (size_t)L.members, 4);
+    W.tend = take(8 * (size_t)ntensors, 8);
+    W.end = W.R.end + (sizeof(tlz::MemberRec) + 4) * (size_t)L.members + 8 * (size_t)ntensors + 32;
     return W;
 }
 

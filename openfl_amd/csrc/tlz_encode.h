@@ -130,6 +130,22 @@ struct EncArgs {
     int32_t lab_n;
 };
 constexpr int kEncPhases = 16;
+// The table-driven variant (k_tlz_encode<true>, ofl_gzip_ranks_batch): the
+// streams of many tensors of one arena in one launch.  Block j of the launch
+// whose first member is mem0 encodes member m = order[mem0 + j] of it: values
+// x[tab[mem0 + m].start ...], tab[mem0 + m].count of them, into slot m, sizes[m]
+// and ops row m -- the order (members by count descending) decides only which
+// member starts when, never where its bytes go.  n and aligned are unused: a
+// member starts at any element position, so whether its loads may be 16 bytes
+// wide is found per member.
+struct EncTabArgs : EncArgs {
+    const MemberRec* tab;    // [members], table order
+    const int32_t* order;    // [members], per launch
+};
+template <bool kTab>
+struct EncArgsOf { using type = EncArgs; };
+template <>
+struct EncArgsOf<true> { using type = EncTabArgs; };
 
 // k-means label of one value (k_bkm_label's rule, lossy_kmeans.h)
 DEVI float lab_rank(float v, const float* m, const float* r) {
@@ -274,7 +290,10 @@ DEVI uint32_t block_scan(uint32_t v, uint32_t* scan, uint32_t* total) {
     return base + inc - v;
 }
 
-__global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_tlz_encode(EncArgs a) {  // 2 blocks per CU: 4 waves per SIMD
+// kTab = false: one contiguous stream, member mem0 + blockIdx.x of it;
+// kTab = true: the member the table names (EncTabArgs)
+template <bool kTab>
+__global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_tlz_encode(typename EncArgsOf<kTab>::type a) {  // 2 blocks per CU: 4 waves per SIMD
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     EncSmem& S = *reinterpret_cast<EncSmem*>(smem_raw);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -287,10 +306,22 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         if (ph_on) { const uint64_t t = wall_clock64(); if (k > 0) ph_acc[k] += t - ph_t; ph_t = t; }
     };
     PH(0);
-    const int64_t g0 = (a.mem0 + blockIdx.x) * (int64_t)kMemTok;
-    const int ntok = (int)min<int64_t>(kMemTok, a.n - g0);
+    uint32_t mi = blockIdx.x;  // the member within the launch: its slot, its sizes entry, its ops row
+    int64_t g0;
+    int ntok, aligned;
+    if constexpr (kTab) {
+        mi = (uint32_t)a.order[a.mem0 + blockIdx.x];
+        const MemberRec r = a.tab[a.mem0 + mi];
+        g0 = r.start;
+        ntok = r.count;
+        aligned = (reinterpret_cast<uintptr_t>(a.x + g0) & 15u) == 0;
+    } else {
+        g0 = (a.mem0 + blockIdx.x) * (int64_t)kMemTok;
+        ntok = (int)min<int64_t>(kMemTok, a.n - g0);
+        aligned = a.aligned;
+    }
     const int nseg = (ntok + kSeg - 1) >> kSegLog;
-    uint32_t* const ops = a.ops + (int64_t)blockIdx.x * a.ops_stride;
+    uint32_t* const ops = a.ops + (int64_t)mi * a.ops_stride;
     if (tid < 256) {
         uint32_t r = (uint32_t)tid;
         for (int k = 0; k < 8; ++k) r = (r & 1u) ? (r >> 1) ^ 0xEDB88320u : r >> 1;
@@ -350,7 +381,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         {
             const int nv = max(0, min(kPer, send - lo));
             float v[kPer];
-            if (nv == kPer && a.aligned) {
+            if (nv == kPer && aligned) {
                 const float4* p = reinterpret_cast<const float4*>(a.x + g0 + lo);
 #pragma unroll
                 for (int u = 0; u < kPer / 4; ++u) {
@@ -421,7 +452,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
         __syncthreads();
         if (S.bad) {  // block-uniform
-            if (tid == 0) { atomicOr(a.bad, 1); a.sizes[blockIdx.x] = 0; }
+            if (tid == 0) { atomicOr(a.bad, 1); a.sizes[mi] = 0; }
             return;
         }
         PH(1);
@@ -984,7 +1015,7 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const uint32_t pos0 = H + block_scan<kNT>(mine, S.scan, &tot);
     if (tid == 0) S.total_bits = H + tot;
     const uint32_t D = (uint32_t)hdr_bytes(nseg);  // header bytes (a multiple of 4)
-    uint32_t* const slot = reinterpret_cast<uint32_t*>(a.slots + (int64_t)blockIdx.x * a.slot_bytes);
+    uint32_t* const slot = reinterpret_cast<uint32_t*>(a.slots + (int64_t)mi * a.slot_bytes);
     uint32_t* const dw = slot + D / 4;                    // the deflate data's words
     {
         const uint32_t nw = (H + tot + 15u + 7u + 64u + 31u) / 32u + 1u;
@@ -1062,11 +1093,25 @@ __global__ __launch_bounds__(kNT) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         for (int s = 0; s < nseg; ++s)
             for (int i = 0; i < 4; ++i) hb[kHdrFixed + 4 * s + i] = (uint8_t)(S.segbit[s] >> (8 * i));
         for (uint32_t i = 0; i < D / 4; ++i) slot[i] = reinterpret_cast<const uint32_t*>(hb)[i];
-        a.sizes[blockIdx.x] = bytes;
+        a.sizes[mi] = bytes;
     }
     PH(9);
     if (ph_on)
         for (int k = 0; k < kEncPhases; ++k) a.phases[k] = ph_acc[k];
+}
+
+// the batched encoder, behind a launch's scan (off: k_gzip_scan's output for
+// members [c0, c0 + nb) of the table): where each tensor's stream ends in the
+// packed output -- the end of its last member.  Members of a tensor are
+// consecutive and the scan runs on over the launches, so tensor t's stream
+// is [tend[t - 1], tend[t]) (from 0 for the first)
+__global__ __launch_bounds__(kBatch) void k_tlz_tensor_end(const MemberRec* tab, int64_t c0, int nb, int64_t members,
+                                                           const uint64_t* off, uint64_t* tend) {
+    const int i = threadIdx.x;
+    if (i >= nb) return;
+    const int64_t m = c0 + i;
+    const int32_t t = tab[m].tensor;
+    if (m + 1 == members || tab[m + 1].tensor != t) tend[t] = off[i + 1];
 }
 
 }  // namespace tlz

@@ -393,6 +393,48 @@ def gzip_ranks(x, label=None):
     return payload
 
 
+@_on_device
+def gzip_ranks_batch(ranks_arena, offsets, numels):
+    """gzip_ranks of every tensor of an arena in one call (ofl_gzip_ranks_batch):
+    tensor t is ranks_arena[offsets[t]:offsets[t] + numels[t]] and its payload
+    is byte for byte gzip_ranks of that slice.  All tensors' members are
+    encoded in table-driven launches, packed back to back and cross PCIe once,
+    into one pinned buffer the payloads are cut from.  -> list of bytes, one
+    per tensor (gzip of nothing for an empty tensor, which the device call
+    leaves out).  Raises CodecError for values that are not integers 0..31."""
+    _check_dev(ranks_arena)
+    L = _lib.lib()
+    T, off, num = _arena_index(offsets, numels)
+    keep = np.flatnonzero(num > 0)
+    result = [gzip.compress(b"", compresslevel=9) if n == 0 else None for n in num]
+    if keep.size == 0:
+        return result
+    if int((off[keep] + num[keep]).max()) > ranks_arena.numel() or int(off[keep].min()) < 0:
+        raise _lib.CodecError("gzip ranks batch: a tensor lies outside the arena")
+    off, num = np.ascontiguousarray(off[keep]), np.ascontiguousarray(num[keep])
+    nt = int(keep.size)
+    need = int(L.ofl_gzip_ranks_batch_workspace_bytes(nt, num.ctypes.data))
+    bound = int(L.ofl_gzip_ranks_batch_bound(nt, num.ctypes.data))
+    if need == 0:
+        raise _lib.CodecError("gzip ranks batch: too many members")
+    ws = _ws_bytes(ranks_arena.device, need)
+    ends = np.zeros(nt, np.uint64)
+    # the same two-step capacity as gzip_ranks: a quarter of the input, the bound after an OFL_ESPACE
+    for cap in (min(bound, int(num.sum()) + (1 << 20)), bound):
+        out = _buf("host", "gz_out", cap, pinned=True)
+        rc = L.ofl_gzip_ranks_batch(nt, ranks_arena.data_ptr(), off.ctypes.data, num.ctypes.data, out.data_ptr(), cap,
+                                    ends.ctypes.data, ws.data_ptr(), ws.numel(), _stream(ranks_arena.device))
+        if rc != _lib.OFL_ESPACE or cap == bound:
+            break
+    _lib.check_gzip(rc)
+    lo = 0
+    for t, hi in zip(keep, ends):
+        result[t] = hostmem.bytes_from(out.data_ptr() + lo, int(hi) - lo)
+        lo = int(hi)
+    _trim_bufs()
+    return result
+
+
 def gunzip(data, threads=8, out=None):
     """gzip.decompress (kc_pipeline.py:152-156) of `data` -> uint8 numpy array.
     Member-indexed streams (the device gzip's, every member carrying its size

@@ -53,6 +53,20 @@ class GZIPTransformer(Transformer):
                     raise
         return self.forward(ranks_dev.cpu().numpy())
 
+    def forward_device_batch(self, ranks_arena, offsets, numels):
+        """forward_device of every tensor ranks_arena[offsets[t]:offsets[t] +
+        numels[t]] of a float32 device arena -> [(payload, metadata)], the
+        same bytes: with the device backend one batched encode for all of them
+        (lossy.gzip_ranks_batch); with the host backend, or when a value lies
+        outside 0..31, tensor by tensor."""
+        if self.backend == "device":
+            try:
+                return [(p, {}) for p in lossy.gzip_ranks_batch(ranks_arena, offsets, numels)]
+            except lossy._lib.CodecError as e:
+                if "values must be" not in str(e):
+                    raise
+        return [self.forward_device(ranks_arena[int(o):int(o) + int(n)]) for o, n in zip(offsets, numels)]
+
     def backward(self, data, metadata, **kwargs):
         # member-indexed streams inflate on native threads; others via gzip.decompress
         return lossy.gunzip(data, self.threads).view(np.float32)
