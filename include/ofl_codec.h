@@ -700,6 +700,41 @@ int ofl_inflate_tlz_launch_lut(const uint8_t* src, const int64_t* index, int64_t
 int ofl_inflate_tlz_check(int64_t nmembers, void* ws, size_t ws_bytes, void* stream);
 int ofl_inflate_members(const uint8_t* src, const int64_t* index, int64_t nmembers, uint32_t max_isize, uint8_t* out,
                         size_t out_cap, void* ws, size_t ws_bytes, void* stream);
+/* All payloads of one upload in one batch, in the same two steps.
+ * ofl_gzip_member_index_batch (HOST, no GPU, up to nthreads native threads):
+ * payload p = src[p][len[p]] will stand at byte stream_pos[p] of one device
+ * buffer, its tensor at byte out_off[p] of one output arena, and must decode
+ * to expect_bytes[p] bytes.  verdict[p]: 0 the payload is in the index; 1 it
+ * is not member-indexed; 2 not every member is TLZ; 3 its members' ISIZEs do
+ * not add up to expect_bytes[p] -- such a payload is left out (no error) for
+ * the caller's one-stream path.  index (cap_members records, else
+ * OFL_ESPACE): the records of ofl_gzip_member_index with data offsets
+ * shifted by stream_pos and output offsets by out_off -- first the *nlarge
+ * members of more than one segment (ISIZE > 8192), longest first, then the
+ * *nsmall members of one segment, small_payload[i] naming the payload of the
+ * i-th of them.
+ * ofl_inflate_lut_batch: index is the DEVICE copy of that table, src the
+ * DEVICE buffer (16-byte aligned, readable for 128 bytes past the last
+ * payload), small_tensor (DEVICE) the row of lut_tab of each one-segment
+ * member's tensor, lut_* as for ofl_inflate_tlz_launch_lut (lut_n = 0: the
+ * ranks themselves are stored).  One status reset, k_tlz_ops and
+ * k_tlz_resolve over the large members, and k_tlz_small over the
+ * one-segment members -- one wavefront per member, four members per block:
+ * header, symbols, copy resolution, CRC-32, table lookup and the float32
+ * stores without leaving LDS -- all on stream, one synchronisation.
+ * OFL_EFORMAT where the TLZ decoder refused a member (it may still be valid
+ * deflate data: the one-stream calls decide), OFL_EINVAL for a CRC-32 or size
+ * mismatch, OFL_ESPACE for a member outside out.  No fallback runs inside.
+ * ws: DEVICE, ofl_inflate_lut_batch_workspace_bytes(nlarge). */
+int ofl_gzip_member_index_batch(int npayloads, const uint8_t* const* src, const size_t* len, const int64_t* stream_pos,
+                                const int64_t* out_off, const int64_t* expect_bytes, int nthreads, int64_t* index,
+                                int64_t cap_members, int32_t* small_payload, int64_t* nlarge, int64_t* nsmall,
+                                int32_t* verdict);
+size_t ofl_inflate_lut_batch_workspace_bytes(int64_t nlarge);
+int ofl_inflate_lut_batch(const uint8_t* src, const int64_t* index, int64_t nlarge, int64_t nsmall,
+                          const int32_t* small_tensor, uint8_t* out, size_t out_cap, const float* lut_tab,
+                          const int64_t* lut_start, const int64_t* lut_end, int32_t lut_n, void* ws, size_t ws_bytes,
+                          void* stream);
 /* Per-kernel timing of the gzip / inflate launches (bench.py): enable (1)
  * resets and starts recording HIP events around every launch of this
  * process's calls, 0 stops; collect synchronises the recorded events and

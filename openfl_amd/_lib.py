@@ -39,6 +39,7 @@ EXPORTS = (
     "ofl_gzip_ranks_batch_workspace_bytes", "ofl_gzip_ranks_batch_bound", "ofl_gzip_ranks_batch",
     "ofl_gunzip_members", "ofl_gzip_member_index", "ofl_inflate_members", "ofl_inflate_tlz_workspace_bytes",
     "ofl_inflate_tlz", "ofl_inflate_tlz_async", "ofl_inflate_tlz_wait", "ofl_inflate_tlz_launch", "ofl_inflate_tlz_launch_lut", "ofl_inflate_tlz_check", "ofl_gzip_profile", "ofl_gzip_profile_collect",
+    "ofl_gzip_member_index_batch", "ofl_inflate_lut_batch_workspace_bytes", "ofl_inflate_lut_batch",
 )
 
 
@@ -229,6 +230,12 @@ def _bind(L):
     L.ofl_inflate_tlz_launch_lut.restype = i32
     L.ofl_inflate_tlz_check.argtypes = [i64, vp, sz, vp]
     L.ofl_inflate_tlz_check.restype = i32
+    L.ofl_gzip_member_index_batch.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp]
+    L.ofl_gzip_member_index_batch.restype = i32
+    L.ofl_inflate_lut_batch_workspace_bytes.argtypes = [i64]
+    L.ofl_inflate_lut_batch_workspace_bytes.restype = sz
+    L.ofl_inflate_lut_batch.argtypes = [vp, vp, i64, i64, vp, vp, sz, vp, vp, vp, i32, vp, sz, vp]
+    L.ofl_inflate_lut_batch.restype = i32
     L.ofl_gzip_profile.argtypes = [i32]
     L.ofl_gzip_profile.restype = i32
     L.ofl_gzip_profile_collect.argtypes = [vp, sz, vp, vp, i32, vp]

@@ -43,7 +43,6 @@ on the device between rounds (ofl_adaptive_step).
 """
 import collections
 import ctypes
-import zlib
 
 import numpy as np
 import torch
@@ -873,8 +872,9 @@ class RoundEnd:
         RoundEnd's plan (planes gathered into pinned staging, one H2D; the
         decode adds the base itself), so their metadata must name the layout's
         slice plan, as every conforming encoder's does.  KC / SKC / STC: one
-        device inflate with the fused LUT per tensor, into a decode arena of
-        this instance, so `out` is written only once everything has decoded.
+        batched device inflate with the fused LUTs for the whole upload, into
+        a decode arena of this instance, so `out` is written only once
+        everything has decoded.
         Every check of the items (count, int_list against the layout, payload
         lengths, Eden metadata) raises CodecError naming the tensor before
         `out` is written or anything is launched.
@@ -1051,25 +1051,22 @@ class RoundEnd:
         return self._lossy.dev if self._lossy.gz.backend == "device" else []
 
     def _ingest_lossy(self, items, bufs, base, out):
-        """KC / SKC / STC payloads: the pipeline's device backward per tensor
-        (inflate with the fused LUT) straight into the tensor's place in the
-        decode arena; the tensors on the pipeline's host path through its own
-        backward, staged like raw ones.  `out` is written from the decode
-        arena once every tensor has decoded."""
+        """KC / SKC / STC payloads: one batched device inflate with the fused
+        LUTs (lossy.gunzip_lut_batch: one H2D of the streams, one of the
+        member table and the tables, one launch sequence) straight into the
+        tensors' places in the decode arena; the tensors on the pipeline's
+        host path through its own backward, staged like raw ones.  `out` is
+        written from the decode arena once every tensor has decoded."""
         dev = self.device
         inflated = self._inflated()
         host_path = [i for i, n in enumerate(self.numels) if n and i not in set(inflated)]
         st = self._ingest_staging("lossy", host_path)
         dst = self._decode_arena()
         where = 0 if self._lossy.kind == "kc" else 1
-        for i in inflated:
-            o, n = self.offsets[i], self.numels[i]
-            m = items[i][1][where]["int_to_float"]
-            try:
-                lossy.gunzip_device(items[i][0], dst[o:o + n].view(torch.uint8),
-                                    lut=lossy.lut_tables([0], [n], [m], dev), expect_bytes=4 * n)
-            except (_lib.CodecError, EOFError, OSError, zlib.error) as e:   # the last three: the host fallback's
-                raise _lib.CodecError(f"tensor {i}: {e}") from e
+        if inflated:
+            lossy.gunzip_lut_batch([items[i][0] for i in inflated], [self.offsets[i] for i in inflated],
+                                   [self.numels[i] for i in inflated],
+                                   [items[i][1][where]["int_to_float"] for i in inflated], dst, ids=inflated)
         if host_path:
             dec = [np.ascontiguousarray(self.pipeline.backward(items[i][0], list(items[i][1])), np.float32).reshape(-1)
                    for i in host_path]

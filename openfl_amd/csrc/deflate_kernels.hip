@@ -182,6 +182,42 @@ int inflate_tlz_enqueue(const uint8_t* src, const int64_t* index, int64_t first,
     return OFL_OK;
 }
 
+// ofl_inflate_lut_batch: the status reset, the large members' kernel pair and
+// the one-segment members' kernel on one stream, one synchronisation
+int inflate_lut_batch(const uint8_t* src, const int64_t* index, int64_t nlarge, int64_t nsmall,
+                      const int32_t* small_tensor, uint8_t* out, size_t out_cap, const LutDev* lut, void* ws,
+                      size_t ws_bytes, void* stream) {
+    if (nlarge < 0 || nsmall < 0 || nsmall > (int64_t)INT32_MAX * gz::tlz::kSmallWaves)
+        return gzfail(OFL_EINVAL, "inflate batch: bad member counts");
+    if ((nlarge || nsmall) && (!src || !index || !out)) return gzfail(OFL_EINVAL, "inflate batch: null argument");
+    if (nsmall && lut && !small_tensor) return gzfail(OFL_EINVAL, "inflate batch: null small_tensor");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = inflate_tlz_enqueue(src, index, 0, nlarge, out, out_cap, ws, ws_bytes, stream, true, lut)) return rc;
+    if (nsmall) {
+        int* status = reinterpret_cast<int*>(static_cast<char*>(ws) + gz::inflate_ws(nlarge).status);
+        const gz::tlz::SmallArgs a{src, index + gz::kIdxWords * nlarge, small_tensor, nsmall, out, (uint64_t)out_cap,
+                                   status, lut ? lut->tab : nullptr, lut ? lut->n : 0};
+        const dim3 grid((unsigned)((nsmall + gz::tlz::kSmallWaves - 1) / gz::tlz::kSmallWaves));
+        const dim3 block(64 * gz::tlz::kSmallWaves);
+        gzprof_begin(st);
+        if (lut)
+            hipLaunchKernelGGL(gz::tlz::k_tlz_small<true>, grid, block, sizeof(gz::tlz::SmallSmem), st, a);
+        else
+            hipLaunchKernelGGL(gz::tlz::k_tlz_small<false>, grid, block, sizeof(gz::tlz::SmallSmem), st, a);
+        gzprof_end(st, "tlz::k_tlz_small");
+        GZHIP(hipGetLastError());
+    }
+    int h = 0;
+    if (int rc = read_status(ws, st, &h)) return rc;
+    // a refused member may still be valid deflate data (the caller's
+    // one-stream path decides); a CRC-32 or size mismatch is corrupt either way
+    if (h & gz::kInfRange) return gzfail(OFL_ESPACE, "inflate batch: a member's output falls outside out");
+    if (h & gz::kInfCorrupt) return gzfail(OFL_EFORMAT, "inflate batch: the TLZ decoder refused a member");
+    if (h & gz::kInfSize) return gzfail(OFL_EINVAL, "inflate batch: member size differs from its ISIZE");
+    if (h & gz::kInfCrc) return gzfail(OFL_EINVAL, "inflate batch: CRC-32 mismatch");
+    return OFL_OK;
+}
+
 hipError_t gz_device_setup() {
     return ofl_util::per_device_once([] {
         uint32_t m[32][32];
@@ -196,6 +232,12 @@ hipError_t gz_device_setup() {
         if (e == hipSuccess)
             e = hipFuncSetAttribute((const void*)gz::k_inflate_members<65536, false, false>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(gz::InfSmem<65536, false>));
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)gz::tlz::k_tlz_small<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)sizeof(gz::tlz::SmallSmem));
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)gz::tlz::k_tlz_small<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)sizeof(gz::tlz::SmallSmem));
         return e;
     });
 }
@@ -685,6 +727,35 @@ int ofl_gzip_member_index(const uint8_t* src, size_t n, int64_t* index, int64_t 
         gz::idx_pack(index + gz::kIdxWords * i, m.in, m.in_len, m.tlz, m.out, m.isize, m.crc);
     }
     return OFL_OK;
+}
+
+int ofl_gzip_member_index_batch(int npayloads, const uint8_t* const* src, const size_t* len, const int64_t* stream_pos,
+                                const int64_t* out_off, const int64_t* expect_bytes, int nthreads, int64_t* index,
+                                int64_t cap_members, int32_t* small_payload, int64_t* nlarge, int64_t* nsmall,
+                                int32_t* verdict) {
+    if (npayloads < 0 || !nlarge || !nsmall || (npayloads && (!src || !len || !stream_pos || !out_off || !expect_bytes || !verdict)))
+        return gzfail(OFL_EINVAL, "member index batch: null argument");
+    gz::InflateBatchIndex X;
+    gz::inflate_batch_index(npayloads, src, len, stream_pos, out_off, expect_bytes, nthreads, verdict, X);
+    *nlarge = X.nlarge;
+    *nsmall = X.nsmall;
+    if (X.nlarge + X.nsmall > cap_members || ((X.nlarge + X.nsmall) && (!index || !small_payload)))
+        return gzfail(OFL_ESPACE, "member index batch: index array too small");
+    if (!X.rec.empty()) memcpy(index, X.rec.data(), sizeof(int64_t) * X.rec.size());
+    if (!X.small_payload.empty()) memcpy(small_payload, X.small_payload.data(), sizeof(int32_t) * X.small_payload.size());
+    return OFL_OK;
+}
+
+size_t ofl_inflate_lut_batch_workspace_bytes(int64_t nlarge) { return gz::inflate_ws(nlarge).end; }
+
+int ofl_inflate_lut_batch(const uint8_t* src, const int64_t* index, int64_t nlarge, int64_t nsmall,
+                          const int32_t* small_tensor, uint8_t* out, size_t out_cap, const float* lut_tab,
+                          const int64_t* lut_start, const int64_t* lut_end, int32_t lut_n, void* ws, size_t ws_bytes,
+                          void* stream) {
+    if (lut_n < 0 || (lut_n && (!lut_tab || !lut_start || !lut_end))) return gzfail(OFL_EINVAL, "inflate batch: bad LUT");
+    const LutDev lut{lut_tab, lut_start, lut_end, lut_n};
+    return inflate_lut_batch(src, index, nlarge, nsmall, small_tensor, out, out_cap, lut_n ? &lut : nullptr, ws, ws_bytes,
+                             stream);
 }
 
 size_t ofl_inflate_tlz_workspace_bytes(int64_t nmembers) { return gz::inflate_ws(nmembers).end; }

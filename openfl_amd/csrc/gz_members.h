@@ -166,6 +166,69 @@ inline int parse_members(const uint8_t* src, size_t n, unsigned max_threads, siz
     return OFL_OK;
 }
 
+// ---- the batched inflate's member table (ofl_gzip_member_index_batch) -------
+// All payloads of one upload as one index: payload p's bytes will stand at
+// pos[p] of one device buffer and its tensor at byte out_off[p] of one output
+// arena, so its members' data offsets are shifted by the one and their output
+// offsets by the other.  A payload joins the table only if it is
+// member-indexed, all TLZ, and its members' ISIZEs add up to expect[p]; any
+// other keeps its verdict and is left to the caller's one-stream path.
+// The records: members of more than one segment first, longest first (ties in
+// payload and member order), as the batched encoder orders its launches; then
+// the members of one segment (ISIZE <= 4 * kSeg), each with its payload's
+// number in small_payload.
+enum { kBatchOk = 0, kBatchNotIndexed = 1, kBatchNotTlz = 2, kBatchLength = 3 };
+struct InflateBatchIndex {
+    std::vector<int64_t> rec;            // kIdxWords per member: nlarge records, then nsmall
+    std::vector<int32_t> small_payload;  // [nsmall]
+    int64_t nlarge = 0, nsmall = 0;
+};
+inline void inflate_batch_index(int npayloads, const uint8_t* const* src, const size_t* len, const int64_t* pos,
+                                const int64_t* out_off, const int64_t* expect, int nthreads, int32_t* verdict,
+                                InflateBatchIndex& X) {
+    std::vector<std::vector<GzMember>> mem((size_t)std::max(npayloads, 0));
+    const int nt = std::max(1, std::min(nthreads, npayloads));
+    auto work = [&](int t) {
+        for (int p = t; p < npayloads; p += nt) {  // interleaved: neighbours are of like size
+            size_t total = 0;
+            const char* msg = "";
+            bool tl = true;
+            if (!src[p] || len[p] == 0 || parse_members(src[p], len[p], 1, 0, mem[p], total, &msg) != OFL_OK ||
+                mem[p].empty()) {
+                verdict[p] = kBatchNotIndexed;
+            } else {
+                for (const GzMember& m : mem[p]) tl = tl && m.tlz;
+                verdict[p] = !tl ? kBatchNotTlz : (int64_t)total != expect[p] ? kBatchLength : kBatchOk;
+            }
+            if (verdict[p] != kBatchOk) mem[p].clear();
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back(work, t);
+    work(0);
+    for (auto& x : th) x.join();
+    struct Ref { int32_t p; uint32_t i; uint32_t isize; };
+    std::vector<Ref> large, small;
+    for (int p = 0; p < npayloads; ++p)
+        for (size_t i = 0; i < mem[p].size(); ++i) {
+            const uint32_t isz = mem[p][i].isize;
+            (isz > 4u * (uint32_t)tlz::kSeg ? large : small).push_back({p, (uint32_t)i, isz});
+        }
+    std::stable_sort(large.begin(), large.end(), [](const Ref& a, const Ref& b) { return a.isize > b.isize; });
+    X.nlarge = (int64_t)large.size();
+    X.nsmall = (int64_t)small.size();
+    X.rec.resize((size_t)kIdxWords * (large.size() + small.size()));
+    X.small_payload.resize(small.size());
+    int64_t* r = X.rec.data();
+    for (const std::vector<Ref>* part : {&large, &small})
+        for (const Ref& f : *part) {
+            const GzMember& m = mem[f.p][f.i];
+            idx_pack(r, (uint64_t)pos[f.p] + m.in, m.in_len, m.tlz, (uint64_t)out_off[f.p] + m.out, m.isize, m.crc);
+            r += kIdxWords;
+        }
+    for (size_t i = 0; i < small.size(); ++i) X.small_payload[i] = small[i].p;
+}
+
 // ---- the encoder's sizes ----------------------------------------------------
 struct TlzLayout {
     int64_t members, batch;

@@ -616,6 +616,325 @@ __global__ __launch_bounds__(kRNT) void k_tlz_resolve(DecArgs a) {
         else if ((crc_adv(0xffffffffu, isize) ^ S.crc_raw ^ 0xffffffffu) != want_crc) atomicOr(a.status, kInfCrc);
     }
 }
+
+// ---- one-segment members: the whole decode in one wavefront ----------------
+// k_tlz_small: a member of at most kSeg values (a batch-norm vector, a bias)
+// has one segment, so k_tlz_ops would decode it on one lane of a wavefront
+// and k_tlz_resolve would spend a 256-thread block, its table set-up and a
+// round trip of the op records through HBM on it.  Here a wavefront takes the
+// member from its header to its float32 values, kSmallWaves members per
+// block, everything between in the wave's own LDS:
+//   header   the dynamic block header, wave-uniform, into the wave's DecSmem
+//   symbols  lane 0 decodes them into op records (W.opr), with every check
+//            k_tlz_ops applies
+//   expand   the lanes split the ops, a wave scan gives each op's position,
+//            every value's entry is its id or the distance to its source
+//            (W.u.e, over the code tables, which are dead by then)
+//   resolve  pointer jumping on the entries, wave barriers only.  The member
+//            starts at its own position 0, so every source lies inside it:
+//            no value ring, no distance leaves LDS
+//   values   CRC-32 of the ranks (each lane a 32-value chain, advanced to the
+//            member's end and XORed), then the tensor's table -- the index
+//            names the tensor, so one 32-entry load and no range search --
+//            and 16-byte stores wherever the address allows
+// The block's one __syncthreads orders the CRC byte table the waves share.
+constexpr int kSmallWaves = 4;                 // 4 x 21.1 KiB + 1 KiB of LDS: one block per CU's 160 KiB
+constexpr int kSmallRounds = 16;               // pointer jumping halves every chain: <= 1 + log2(kSeg) rounds
+struct SmallArgs {
+    const uint8_t* src;      // as DecArgs::src
+    const int64_t* idx;      // the one-segment members' index records
+    const int32_t* tensor;   // per member: its tensor's row of lut_tab
+    int64_t nmem;
+    uint8_t* out;
+    uint64_t out_cap;
+    int* status;
+    const float* lut_tab;    // [lut_n][32] (LUT), else unused
+    int32_t lut_n;
+};
+struct SmallWave {
+    union {
+        DecSmem dec;                       // header and symbols
+        alignas(16) uint16_t e[kSeg];      // then: 0x8000 | id (resolved) or the distance to the source
+    } u;
+    uint32_t opr[kSeg];                    // op records: 0x80000000 | id, or length | distance << 7 (values)
+    float lt[32];                          // the tensor's table
+};
+struct SmallSmem {
+    uint32_t crct[1][256];
+    SmallWave w[kSmallWaves];
+};
+static_assert(sizeof(SmallSmem) <= 160 * 1024, "k_tlz_small: the block's LDS must fit a CU's 160 KiB");
+
+template <bool LUT>
+__global__ __launch_bounds__(64 * kSmallWaves) void k_tlz_small(SmallArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    SmallSmem& B = *reinterpret_cast<SmallSmem*>(smem_raw);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int i = tid; i < 256; i += 64 * kSmallWaves) {
+        uint32_t r = (uint32_t)i;
+        for (int k = 0; k < 8; ++k) r = (r & 1u) ? (r >> 1) ^ 0xEDB88320u : r >> 1;
+        B.crct[0][i] = r;
+    }
+    __syncthreads();
+    const int64_t m = (int64_t)blockIdx.x * kSmallWaves + wv;
+    if (m >= a.nmem) return;
+    SmallWave& W = B.w[wv];
+    DecSmem& S = W.u.dec;
+    const int64_t* ix = a.idx + kIdxWords * m;
+    const int64_t doff = ix[kIdxIn];
+    const uint32_t in_len = GZ_IDX_IN_LEN(ix[kIdxLen]);
+    const int64_t out_off = ix[kIdxOut];
+    const uint32_t isize = GZ_IDX_ISIZE(ix[kIdxSize]), want_crc = GZ_IDX_CRC(ix[kIdxSize]);
+    const uint8_t* data = a.src + doff;
+    const uint32_t T = isize / 4u;             // the member's values: one segment
+    int err = 0;
+    if ((isize & 3u) || T == 0 || T > (uint32_t)kSeg || (out_off & 3) || out_off < 0 ||
+        (uint64_t)out_off + isize > a.out_cap)
+        err = kInfRange;
+    int row = 0;
+    if (LUT) {
+        row = a.tensor[m];
+        if (row < 0 || row >= a.lut_n) err = kInfRange;
+    }
+    const uint8_t* oz = data - table_bytes(1) - kOzTable;  // the 'OZ' subfield ends where the data starts
+    if (!err) {
+        if (oz[0] != 'O' || oz[1] != 'Z' || oz[kOzVersion] != kVersion || oz[kOzSegLog] != kSegLog ||
+            rd16(oz + kOzNseg) != 1u || rd32(oz + kOzValues) != T)
+            err = kInfCorrupt;
+    }
+    // the segment table (untrusted): its one entry must lie inside the data
+    const uint32_t sb0 = err ? 0u : rd32(data - table_bytes(1));
+    if (!err && (uint64_t)sb0 >= 8ull * (uint64_t)in_len) err = kInfCorrupt;
+    if (err) {
+        if (lane == 0) atomicOr(a.status, err);
+        return;
+    }
+    if (lane < 32) W.lt[lane] = LUT ? a.lut_tab[(int64_t)row * 32 + lane] : (float)lane;
+    const uint64_t dbit = 8ull * (uint64_t)doff;
+    const uint64_t ebit = dbit + 8ull * (uint64_t)in_len;
+    // ---- the block header, on every lane (wave-uniform), as k_tlz_ops ----
+    BitIn in;
+    in.start(a.src, dbit);
+    if (in.get(1) != 1u || in.get(2) != 2u) err = kInfCorrupt;  // BFINAL, dynamic
+    if (!err) {
+        const int nlit = (int)in.get(5) + 257;
+        const int ndist = (int)in.get(5) + 1;
+        const int ncl = (int)in.get(4) + 4;
+        if (nlit > 286 || ndist > 30) err = kInfCorrupt;
+        for (int i = lane; i < 19; i += 64) S.lens[i] = 0;
+        __builtin_amdgcn_wave_barrier();
+        for (int i = 0; i < ncl && !err; ++i) {
+            in.fill();
+            const uint32_t v = in.get(3);
+            if (lane == 0) S.lens[c_clord[i]] = (uint8_t)v;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (!err && !inf_build(S.lit, S.lens, 19, kAlphaPlain, kSetFull)) err = kInfCorrupt;
+        const int total = nlit + ndist;
+        int i = 0;
+        while (!err && i < total) {
+            if (in.pos() > ebit) { err = kInfCorrupt; break; }  // ran past the data (wave-uniform)
+            in.fill();
+            const uint32_t e = S.lit.fast[in.peek() & (uint32_t)(DecLit::kSize - 1)];
+            const int l = (int)(e & 15u);
+            if (!l || (e & 0x300u)) { err = kInfCorrupt; break; }
+            in.drop(l);
+            const int sy = (int)(e >> 16);
+            if (sy < 16) {
+                if (lane == 0) S.lens[i] = (uint8_t)sy;
+                ++i;
+                continue;
+            }
+            int rep, val = 0;
+            if (sy == 16) {
+                if (i == 0) { err = kInfCorrupt; break; }
+                __builtin_amdgcn_wave_barrier();
+                val = S.lens[i - 1];
+                rep = 3 + (int)in.get(2);
+            } else if (sy == 17) {
+                rep = 3 + (int)in.get(3);
+            } else {
+                rep = 11 + (int)in.get(7);
+            }
+            if (i + rep > total) { err = kInfCorrupt; break; }
+            __builtin_amdgcn_wave_barrier();
+            for (int k = lane; k < rep; k += 64) S.lens[i + k] = (uint8_t)val;
+            __builtin_amdgcn_wave_barrier();
+            i += rep;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (!err) {  // every code must fit the first-level tables (the encoder limits them)
+            bool longc = false;
+            for (int k = lane; k < total; k += 64) longc |= S.lens[k] > (k < nlit ? kDecLitBits : kDecDistBits);
+            if (__ballot(longc) || S.lens[256] == 0) err = kInfCorrupt;
+        }
+        if (!err) {
+            const uint8_t dl = lane < ndist ? S.lens[nlit + lane] : 0;
+            __builtin_amdgcn_wave_barrier();
+            for (int k = nlit + lane; k < 288; k += 64) S.lens[k] = 0;
+            __builtin_amdgcn_wave_barrier();
+            if (lane < 32) S.lens[288 + lane] = lane < ndist ? dl : 0;
+            __builtin_amdgcn_wave_barrier();
+            if (!inf_build(S.lit, S.lens, nlit, kAlphaLit, kSetLone) || !inf_build(S.dist, S.lens + 288, ndist, kAlphaDist, kSetLone)) err = kInfCorrupt;
+        }
+        if (!err && in.pos() != dbit + sb0) err = kInfCorrupt;  // the ops start where the table says
+    }
+    if (err) {
+        if (lane == 0) atomicOr(a.status, err);
+        return;
+    }
+    __builtin_amdgcn_wave_barrier();
+    // ---- lane 0: the symbols into op records (the reader stands at the first one) ----
+    uint32_t nops = 0;
+    if (lane == 0) {
+        uint32_t produced = 0;
+        // a corrupt member must not decode on past its data: stop once the bit
+        // window's block passes the data's last block + 1 (as k_tlz_ops)
+        const int64_t blim = (int64_t)(ebit >> 7) + 1;
+        while (produced < T) {  // nops <= produced < T <= kSeg: the records fit W.opr
+            if (in.blk > blim) { err = kInfCorrupt; break; }
+            in.fill();
+            uint32_t e = S.lit.fast[in.peek() & (uint32_t)(DecLit::kSize - 1)];
+            int l = (int)(e & 15u);
+            if (!l) { err = kInfCorrupt; break; }
+            in.drop(l);
+            const uint32_t kind = (e >> 8) & 3u;
+            if (kind == (uint32_t)kKindLit) {  // a value's 4 literal bytes
+                uint32_t bytes = e >> 16;
+                in.fill();
+#pragma unroll
+                for (int y = 1; y < 4; ++y) {
+                    e = S.lit.fast[in.peek() & (uint32_t)(DecLit::kSize - 1)];
+                    l = (int)(e & 15u);
+                    if (!l || ((e >> 8) & 3u) != (uint32_t)kKindLit) { err = kInfCorrupt; break; }
+                    in.drop(l);
+                    bytes |= (e >> 16) << (8 * y);
+                }
+                if (err) break;
+                const float f = __uint_as_float(bytes);
+                const int id = (int)f;
+                if (!(id >= 0 && id < 32 && __float_as_uint((float)id) == bytes)) { err = kInfCorrupt; break; }
+                W.opr[nops++] = 0x80000000u | (uint32_t)id;
+                produced += 1;
+            } else if (kind == (uint32_t)kKindCopy) {
+                const uint32_t len = (e >> 16) + in.get((int)((e >> 4) & 15u));
+                in.fill();
+                const uint32_t f = S.dist.fast[in.peek() & (uint32_t)(DecDist::kSize - 1)];
+                const int l2 = (int)(f & 15u);
+                in.drop(l2);  // (l2 == 0 or a wrong kind fails below, before anything is used)
+                const uint32_t d = (f >> 16) + in.get((int)((f >> 4) & 15u));
+                const uint32_t lt = len >> 2, dt = d >> 2;
+                const bool bad = (l2 == 0) | (((f >> 8) & 3u) != (uint32_t)kKindCopy) | (((len | d) & 3u) != 0u) |
+                                 (lt - (uint32_t)kMinL > (uint32_t)(kMaxL - kMinL)) | (produced + lt > T) |
+                                 (dt > produced);  // no source before the member's first value
+                if (bad) { err = kInfCorrupt; break; }
+                W.opr[nops++] = lt | (dt << 7);
+                produced += lt;
+            } else {
+                err = kInfCorrupt;
+                break;
+            }
+        }
+        if (!err) {  // end of block, then the data ends at the next byte boundary
+            in.fill();
+            const uint32_t e = S.lit.fast[in.peek() & (uint32_t)(DecLit::kSize - 1)];
+            const int l = (int)(e & 15u);
+            if (!l || ((e >> 8) & 3u) != (uint32_t)kKindEnd) err = kInfCorrupt;
+            else {
+                in.drop(l);
+                if ((in.pos() - dbit + 7u) / 8u != in_len) err = kInfCorrupt;
+            }
+        }
+    }
+    err = __builtin_amdgcn_readfirstlane(err);
+    nops = (uint32_t)__builtin_amdgcn_readfirstlane((int)nops);
+    if (err) {
+        if (lane == 0) atomicOr(a.status, err);
+        return;
+    }
+    __builtin_amdgcn_wave_barrier();  // the code tables are dead: W.u.e takes their place
+    // ---- expand: each lane a contiguous run of ops, positions by a wave scan ----
+    {
+        const uint32_t o_lo = nops * (uint32_t)lane / 64u, o_hi = nops * (uint32_t)(lane + 1) / 64u;
+        uint32_t run = 0;
+        for (uint32_t o = o_lo; o < o_hi; ++o) { const uint32_t r = W.opr[o]; run += (r >> 31) ? 1u : (r & 127u); }
+        uint32_t inc = run;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t t = (uint32_t)__shfl_up((int)inc, o, 64);
+            if (lane >= o) inc += t;
+        }
+        if ((uint32_t)__shfl((int)inc, 63, 64) != T) {  // (the symbol loop ends at T: defensive, wave-uniform)
+            if (lane == 0) atomicOr(a.status, kInfCorrupt);
+            return;
+        }
+        uint32_t p = inc - run;
+        for (uint32_t o = o_lo; o < o_hi; ++o) {
+            const uint32_t r = W.opr[o];
+            if (r >> 31) {
+                W.u.e[p++] = (uint16_t)(0x8000u | (r & 31u));
+            } else {
+                const uint32_t l = r & 127u, d = r >> 7;  // d <= p < kSeg: 15 bits hold any summed distance
+                for (uint32_t k = 0; k < l; ++k) W.u.e[p + k] = (uint16_t)d;
+                p += l;
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // ---- resolve: an unresolved entry points at its source, which lies in the member ----
+    {
+        constexpr int kPer = kSeg / 64;
+        static_assert(kPer == 32, "one mask bit per entry of a lane");
+        uint32_t um = 0xffffffffu;  // entries this lane has not seen resolved
+        int rounds = 0;
+#pragma unroll 1
+        for (;;) {
+            uint32_t nm = 0;
+#pragma unroll
+            for (int i = 0; i < kPer; ++i) {
+                const uint32_t k = (uint32_t)lane + 64u * (uint32_t)i;
+                if (!((um >> i) & 1u) || k >= T) continue;
+                const uint32_t e = W.u.e[k];
+                if (e & 0x8000u) continue;
+                const uint32_t es = W.u.e[k - e];  // e <= k: checked as dt <= produced
+                const uint32_t ne = (es & 0x8000u) ? es : e + es;
+                W.u.e[k] = (uint16_t)ne;
+                if (!(ne & 0x8000u)) nm |= 1u << i;
+            }
+            um = nm;
+            __builtin_amdgcn_wave_barrier();
+            if (!__ballot(nm != 0u)) break;
+            if (++rounds == kSmallRounds) {  // cannot happen for checked ops; never spin on it
+                if (lane == 0) atomicOr(a.status, kInfCorrupt);
+                return;
+            }
+        }
+    }
+    // ---- CRC-32 of the ranks: lane l the chain of values [32 l, 32 l + 32) ----
+    {
+        const int k0 = 32 * lane;
+        const int nv = max(0, min(32, (int)T - k0));
+        uint32_t crc = 0;
+        for (int q = 0; q < nv; ++q) crc = crc4(B.crct, crc, __float_as_uint((float)(W.u.e[k0 + q] & 31u)));
+        uint32_t x = nv ? crc_adv(crc, 4u * (uint32_t)((int)T - k0 - nv)) : 0u;
+        for (int o = 32; o > 0; o >>= 1) x ^= (uint32_t)__shfl_xor((int)x, o, 64);
+        if (lane == 0 && (crc_adv(0xffffffffu, isize) ^ x ^ 0xffffffffu) != want_crc) atomicOr(a.status, kInfCrc);
+    }
+    // ---- values: scalar stores up to the first 16-byte boundary and past the last ----
+    {
+        float* const yo = reinterpret_cast<float*>(a.out + out_off);
+        const uint32_t head = min(T, (uint32_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(yo) & 15u)) & 15u) >> 2);
+        if ((uint32_t)lane < head) yo[lane] = W.lt[W.u.e[lane] & 31u];
+        for (uint32_t k = head + 4u * (uint32_t)lane; k < T; k += 256u) {
+            if (k + 4u <= T) {
+                *reinterpret_cast<float4*>(yo + k) = make_float4(W.lt[W.u.e[k] & 31u], W.lt[W.u.e[k + 1] & 31u],
+                                                                 W.lt[W.u.e[k + 2] & 31u], W.lt[W.u.e[k + 3] & 31u]);
+            } else {
+                for (uint32_t q = k; q < T; ++q) yo[q] = W.lt[W.u.e[q] & 31u];
+            }
+        }
+    }
+}
 }  // namespace tlz
 
 // members -> one contiguous stream (slots of any stride).  The destination is

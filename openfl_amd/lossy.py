@@ -10,6 +10,7 @@ import functools
 import gzip
 import os
 import threading
+import zlib
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -512,6 +513,21 @@ def lut_tables(offsets, numels, maps, device):
     kc_pipeline.py:79-83) applied to every rank 0..31, in float32 as
     lut_decode_batch compares and assigns; with the tensors' element ranges
     [offsets[t], offsets[t] + numels[t]) of the decoded arena.  One H2D."""
+    blob, _ = _lut_blob(offsets, numels, maps)
+    return _lut_views(torch.from_numpy(blob).to(torch.device(device)), offsets, numels, maps)
+
+
+def _lut_views(d, offsets, numels, maps):
+    """lut_tables' dict over the device copy d of _lut_blob's bytes."""
+    T = len(numels)
+    return {"tab": d[:128 * T].view(torch.float32), "start": d[128 * T:136 * T].view(torch.int64),
+            "end": d[136 * T:144 * T].view(torch.int64),
+            "n": T, "offsets": list(offsets), "numels": list(numels), "maps": list(maps)}
+
+
+def _lut_blob(offsets, numels, maps):
+    """lut_tables on the host -> (uint8 array of 144 bytes per tensor: the
+    tables, the starts, the ends, sorted by start; each tensor's row)."""
     T = len(numels)
     lens = [len(m) for m in maps]
     mk = max(lens + [1])
@@ -532,10 +548,105 @@ def lut_tables(offsets, numels, maps, device):
     order = np.argsort(start, kind="stable")
     blob = np.concatenate([tab[order].reshape(-1).view(np.uint8), start[order].view(np.uint8),
                            (start + np.asarray(numels, np.int64))[order].view(np.uint8)])
-    d = torch.from_numpy(blob).to(torch.device(device))
-    return {"tab": d[:128 * T].view(torch.float32), "start": d[128 * T:136 * T].view(torch.int64),
-            "end": d[136 * T:144 * T].view(torch.int64),
-            "n": T, "offsets": list(offsets), "numels": list(numels), "maps": list(maps)}
+    row = np.empty(T, np.int32)
+    row[order] = np.arange(T, dtype=np.int32)
+    return blob, row
+
+
+@_on_device
+def gunzip_lut_batch(payloads, offsets, numels, maps, out_arena, ids=None):
+    """gunzip_device(payloads[t], out_arena[offsets[t]:offsets[t] + numels[t]],
+    lut=lut_tables of maps[t], expect_bytes=4 * numels[t]) for every tensor t
+    of one upload, bit for bit, as one device batch: the payloads gathered into
+    pinned staging (ofl_host_copy_many) and sent in one H2D; one member table
+    for all of them built on native threads (ofl_gzip_member_index_batch) and
+    sent with the tensors' tables in a second H2D; one ofl_inflate_lut_batch --
+    the members of one segment (tensors up to 2048 values, and the short last
+    members of others) decoded whole by one wavefront each (k_tlz_small), the
+    rest by k_tlz_ops / k_tlz_resolve in one launch pair.  maps=None: the
+    ranks themselves are stored.
+    A payload the table leaves out (gzip.compress output, BGZF members, a
+    length other than 4 * numels[t]) goes through gunzip_device alone; if the
+    batch reports anything but success, every payload does, in order, so a bad
+    payload raises exactly what it raises there: CodecError "tensor <ids[t]>:
+    ..." (ids: the tensors' names in messages, default their positions).
+    numels[t] >= 1.  -> out_arena."""
+    _check_dev(out_arena)
+    L = _lib.lib()
+    dev = out_arena.device
+    T, off, num = _arena_index(offsets, numels)
+    ids = list(range(T)) if ids is None else list(ids)
+    if T == 0:
+        return out_arena
+    if int(num.min()) < 1 or int(off.min()) < 0 or int((off + num).max()) > out_arena.numel():
+        raise _lib.CodecError("gunzip batch: an empty tensor, or one outside the arena")
+
+    def one(t):
+        o, n = int(off[t]), int(num[t])
+        try:
+            gunzip_device(payloads[t], out_arena[o:o + n].view(torch.uint8),
+                          lut=lut_tables([0], [n], [maps[t]], dev) if maps is not None else None, expect_bytes=4 * n)
+        except (_lib.CodecError, EOFError, OSError, zlib.error) as e:   # the last three: the host fallback's
+            raise _lib.CodecError(f"tensor {ids[t]}: {e}") from e
+
+    srcs = [np.frombuffer(p, np.uint8) for p in payloads]
+    size = np.array([s.size for s in srcs], np.int64)
+    pos = np.zeros(T, np.int64)
+    np.cumsum((size[:-1] + 15) // 16 * 16, out=pos[1:])
+    total = int(pos[-1] + size[-1]) + 128    # the decoders' look-ahead past the last payload
+    done = getattr(_tls, "gzb_done", None)
+    if done is not None:
+        done.synchronize()                   # the previous batch's copies have left the staging
+    stage = _buf("host", "gzb_in", total, pinned=True)
+    ptr = np.array([s.ctypes.data if s.size else 0 for s in srcs], np.uint64)
+    dst = np.uint64(stage.data_ptr()) + pos.astype(np.uint64)
+    _lib.check(L.ofl_host_copy_many(T, dst.ctypes.data, ptr.ctypes.data, size.ctypes.data, _GZ_COPY_THREADS))
+    d_in = _buf(dev, "gzb_in", total)
+    d_in[:total].copy_(stage[:total], non_blocking=True)
+    done = _tls.gzb_done = torch.cuda.Event()
+    done.record()
+    # the index of all members while the streams cross (a member takes >= 26 bytes)
+    cap = int(size.sum()) // 26 + T
+    idx = np.empty((cap, 4), np.int64)
+    small = np.empty(cap, np.int32)
+    verdict = np.zeros(T, np.int32)
+    nl, ns = ctypes.c_int64(), ctypes.c_int64()
+    out_off, expect, usize = 4 * off, 4 * num, size.astype(np.uint64)
+    _lib.check_gzip(L.ofl_gzip_member_index_batch(T, ptr.ctypes.data, usize.ctypes.data, pos.ctypes.data,
+                                                  out_off.ctypes.data, expect.ctypes.data, _GZ_COPY_THREADS,
+                                                  idx.ctypes.data, cap, small.ctypes.data, ctypes.byref(nl),
+                                                  ctypes.byref(ns), verdict.ctypes.data))
+    nl, ns = nl.value, ns.value
+    rc = _lib.OFL_OK
+    if nl + ns:
+        # [tables, starts, ends | index | the small members' table rows]: one copy
+        if maps is not None:
+            lut, row = _lut_blob(off, num, maps)
+        else:
+            lut, row = np.empty(0, np.uint8), np.zeros(T, np.int32)
+        parts = [lut, idx[:nl + ns].view(np.uint8).reshape(-1), row[small[:ns]].view(np.uint8)]
+        nb = sum(p.size for p in parts)
+        hblob = _buf("host", "gzb_tab", nb, pinned=True)
+        hblob.numpy()[:nb] = np.concatenate(parts)
+        d = _buf(dev, "gzb_tab", nb)
+        d[:nb].copy_(hblob[:nb], non_blocking=True)
+        done.record()
+        at_idx = lut.size
+        at_row = at_idx + 32 * (nl + ns)
+        tv = _lut_views(d, off, num, maps) if maps is not None else None
+        ws = _buf(dev, "gz_status", int(L.ofl_inflate_lut_batch_workspace_bytes(nl)))
+        rc = L.ofl_inflate_lut_batch(d_in.data_ptr(), d.data_ptr() + at_idx, nl, ns, d.data_ptr() + at_row,
+                                     out_arena.data_ptr(), 4 * out_arena.numel(),
+                                     tv["tab"].data_ptr() if tv else None, tv["start"].data_ptr() if tv else None,
+                                     tv["end"].data_ptr() if tv else None, T if tv else 0, ws.data_ptr(), ws.numel(),
+                                     _stream(dev))
+        if rc == _lib.OFL_EHIP:
+            _lib.check_gzip(rc)
+    for t in range(T):   # the batch's payloads too where it failed: the one-stream path names the bad one
+        if rc != _lib.OFL_OK or verdict[t]:
+            one(t)
+    _trim_bufs()
+    return out_arena
 
 
 @_on_device

@@ -10,7 +10,8 @@ is exact (sequential key->value replacement emulated per element).
 import numpy as np
 
 from openfl_amd.pipelines.lossy_common import (GZIPTransformer, float_to_int, gzip_lut_backward_device,
-                                               kmeans_ranks, lut_backward, PerThreadDevice, to_device)
+                                               kmeans_ranks, lut_backward, lut_backward_batch, PerThreadDevice,
+                                               to_device)
 from openfl_amd.pipelines.pipeline import TransformationPipeline, Transformer
 
 
@@ -76,3 +77,8 @@ class KCPipeline(TransformationPipeline):
         shape = list(md["int_list"])
         y = gzip_lut_backward_device(data, md["int_to_float"], int(np.prod(shape)) if shape else 1, km.device)
         return y.cpu().numpy().reshape(shape)
+
+    def backward_batch(self, items):
+        """[backward(data, metadata list) for ...] of one upload in one device
+        batch (lossy_common.lut_backward_batch); the metadata lists stay."""
+        return lut_backward_batch(self, items, 0, self.transformers[0].device)

@@ -89,6 +89,35 @@ def gzip_lut_backward_device(data, int2float_map, n, device):
     return raw.view(torch.float32)
 
 
+def lut_backward_batch(pipeline, items, where, device):
+    """backward_batch of a KC / SKC / STC pipeline: [pipeline.backward(data,
+    metadata list) for data, metadata list in items] as float32 arrays, bit for
+    bit, with the device gzip backend in one batch -- the tensors laid out in
+    one device arena from their int_lists, every payload inflated through its
+    LUT by lossy.gunzip_lut_batch, one D2H, views reshaped.  where: the
+    position of the int_to_float metadata.  Empty tensors, and everything
+    with the host gzip backend, go through backward.  Like RoundEnd.ingest,
+    and unlike backward, it leaves the metadata lists as they are."""
+    items = list(items)
+    shapes = [[int(d) for d in mds[0]["int_list"]] for _, mds in items]
+    numels = [int(np.prod(s)) if s else 1 for s in shapes]
+    batch = [i for i, n in enumerate(numels) if n] if pipeline.transformers[-1].backend == "device" else []
+    out = [None] * len(items)
+    if batch:
+        offsets = np.zeros(len(batch), np.int64)
+        np.cumsum([(numels[i] + 3) // 4 * 4 for i in batch[:-1]], out=offsets[1:])   # 16-byte aligned tensors
+        arena = torch.empty(int(offsets[-1]) + numels[batch[-1]], dtype=torch.float32, device=device)
+        lossy.gunzip_lut_batch([items[i][0] for i in batch], offsets, [numels[i] for i in batch],
+                               [items[i][1][where]["int_to_float"] for i in batch], arena, ids=batch)
+        host = arena.cpu().numpy()
+        for i, o in zip(batch, offsets):
+            out[i] = host[int(o):int(o) + numels[i]].reshape(shapes[i])
+    for i, (data, mds) in enumerate(items):
+        if out[i] is None:
+            out[i] = pipeline.backward(data, list(mds))
+    return out
+
+
 def to_device(data, device):
     flat = np.ascontiguousarray(np.asarray(data).reshape(-1), dtype=np.float32)
     if not flat.flags.writeable:  # torch.from_numpy needs a writable buffer
@@ -120,4 +149,4 @@ def lut_backward(data, int2float_map, device):
 
 
 __all__ = ["GZIPTransformer", "PerThreadDevice", "float_to_int", "gzip_lut_backward_device", "kmeans_ranks", "lut_backward",
-           "resolve_device", "to_device"]
+           "lut_backward_batch", "resolve_device", "to_device"]

@@ -7,7 +7,8 @@ on the GPU (see stc_pipeline / kc_pipeline for the parity notes).
 import numpy as np
 
 from openfl_amd.pipelines.lossy_common import (GZIPTransformer, float_to_int, gzip_lut_backward_device,
-                                               kmeans_ranks, lut_backward, PerThreadDevice, to_device)
+                                               kmeans_ranks, lut_backward, lut_backward_batch, PerThreadDevice,
+                                               to_device)
 from openfl_amd.pipelines.pipeline import TransformationPipeline, Transformer
 from openfl_amd.pipelines.stc_pipeline import SparsityTransformer
 
@@ -66,6 +67,11 @@ class SKCPipeline(TransformationPipeline):
         shape = list(transformer_metadata.pop()["int_list"])
         y = gzip_lut_backward_device(data, m, int(np.prod(shape)) if shape else 1, sp.device)
         return y.cpu().numpy().reshape(shape)
+
+    def backward_batch(self, items):
+        """[backward(data, metadata list) for ...] of one upload in one device
+        batch (lossy_common.lut_backward_batch); the metadata lists stay."""
+        return lut_backward_batch(self, items, 1, self.transformers[0].device)
 
 
 __all__ = ["GZIPTransformer", "KmeansTransformer", "SKCPipeline", "SparsityTransformer"]

@@ -10,7 +10,7 @@ import numpy as np
 
 from openfl_amd import lossy
 from openfl_amd.pipelines.lossy_common import (GZIPTransformer, float_to_int, gzip_lut_backward_device, lut_backward,
-                                               PerThreadDevice, to_device)
+                                               lut_backward_batch, PerThreadDevice, to_device)
 from openfl_amd.pipelines.pipeline import TransformationPipeline, Transformer
 
 
@@ -101,6 +101,11 @@ class STCPipeline(TransformationPipeline):
         shape = list(transformer_metadata.pop()["int_list"])
         y = gzip_lut_backward_device(data, m, int(np.prod(shape)) if shape else 1, sp.device)
         return y.cpu().numpy().reshape(shape)
+
+    def backward_batch(self, items):
+        """[backward(data, metadata list) for ...] of one upload in one device
+        batch (lossy_common.lut_backward_batch); the metadata lists stay."""
+        return lut_backward_batch(self, items, 1, self.transformers[0].device)
 
 
 __all__ = ["GZIPTransformer", "STCPipeline", "SparsityTransformer", "TernaryTransformer", "float_to_int"]

@@ -15,6 +15,8 @@ One process, windows alternated (A B A B A B, the minimum and the spread of each
               against k_wavg_delta (4 C + 4 + 4 B/element) in bytes per second.
   ingest      one Eden-coded upload into an arena: ingest() against
               backward_batch() + pack(), the route through host arrays.
+  --lossy-ingest   instead: one KC-, SKC- and STC-coded upload, ingest()
+              against the per-tensor inflate loop it replaced (lossy_ingest).
 Prints one JSON line.
 """
 import argparse
@@ -32,6 +34,100 @@ PEAK_HBM_GBPS = 8000.0
 WINDOWS = 3
 
 
+def lossy_ingest(args):
+    """--lossy-ingest: ingest of one KC-, SKC- and STC-coded upload (the payloads
+    of RoundEnd.run) against the per-tensor loop it replaces -- one lut_tables
+    H2D and one gunzip_device per tensor, written out below as the parent
+    commit had it --, alternated windows; and, with ofl_gzip_profile, the
+    kernels on the tensors of at most 2048 values alone: k_tlz_small against
+    the k_tlz_ops + k_tlz_resolve pairs."""
+    import ctypes
+    import torch
+    from openfl_amd import _lib, lossy
+    from openfl_amd import aggregation as A
+    from openfl_amd import pipelines as P
+    from openfl_amd.workloads import WORKLOADS
+    dev = torch.device("cuda", 0)
+    L = _lib.lib()
+    shapes = [tuple(s) for _, s in WORKLOADS[args.workload]()]
+
+    def timed(fn, steps):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / steps
+
+    def kernel_ms(fn):
+        """{kernel name: [ms, launches]} of one fn() under ofl_gzip_profile."""
+        names, ms, ln, nk = ctypes.create_string_buffer(8192), np.zeros(64), np.zeros(64, np.int64), ctypes.c_int()
+        _lib.check_gzip(L.ofl_gzip_profile(1))
+        try:
+            fn()
+            torch.cuda.synchronize()
+            _lib.check_gzip(L.ofl_gzip_profile_collect(names, 8192, ms.ctypes.data, ln.ctypes.data, 64, ctypes.byref(nk)))
+        finally:
+            L.ofl_gzip_profile(0)
+        return {k: [round(float(ms[i]), 4), int(ln[i])] for i, k in enumerate(names.value.decode().split("\n")[:nk.value])}
+
+    result = {}
+    for name, pipe in (("kc", P.KCPipeline(device=dev)), ("skc", P.SKCPipeline(device=dev)), ("stc", P.STCPipeline(device=dev))):
+        re = A.RoundEnd(pipe, shapes, dev)
+        g = torch.Generator(device=dev)
+        g.manual_seed(7)
+        x = torch.empty(re.arena_numel, dtype=torch.float32, device=dev).normal_(0.0, 0.01, generator=g)
+        re._zero_gaps(x)
+        np.random.seed(0)
+        items = re.run([x], [1.0], None, payloads=True)[1]
+        out = torch.empty_like(x)
+        where = 0 if name == "kc" else 1
+        inflated = re._inflated()
+        small = [i for i in inflated if re.numels[i] <= 2048]
+
+        def loop(tensors, dst):
+            for i in tensors:
+                o, n = re.offsets[i], re.numels[i]
+                lossy.gunzip_device(items[i][0], dst[o:o + n].view(torch.uint8),
+                                    lut=lossy.lut_tables([0], [n], [items[i][1][where]["int_to_float"]], dev),
+                                    expect_bytes=4 * n)
+
+        def batch(tensors, dst):
+            lossy.gunzip_lut_batch([items[i][0] for i in tensors], [re.offsets[i] for i in tensors],
+                                   [re.numels[i] for i in tensors],
+                                   [items[i][1][where]["int_to_float"] for i in tensors], dst)
+
+        def parent_ingest():
+            dst = re._decode_arena()
+            loop(inflated, dst)
+            out[:re.arena_numel].copy_(dst)
+
+        def ingest():
+            re.ingest(items, delta=False, out=out)
+
+        assert len(inflated) == sum(1 for n in re.numels if n), "a host-path tensor: the parent route below has none"
+        parent_ingest()
+        want = out.clone()
+        ingest()
+        same = bool(torch.equal(want.view(torch.int32), out.view(torch.int32)))
+        t = {"ingest": [], "parent_loop": []}
+        for _ in range(WINDOWS):
+            t["ingest"].append(timed(ingest, args.ingest_steps))
+            t["parent_loop"].append(timed(parent_ingest, args.ingest_steps))
+        dst = re._decode_arena()
+        result[name] = {"tensors": len(inflated), "small_tensors": len(small),
+                        "wire_bytes": sum(len(p) for p, _ in items), "same_bits": same,
+                        "ingest_ms": {"min": round(min(t["ingest"]), 4), "max": round(max(t["ingest"]), 4)},
+                        "parent_loop_ms": {"min": round(min(t["parent_loop"]), 4), "max": round(max(t["parent_loop"]), 4)},
+                        "kernels_small_tensors": {"batch": kernel_ms(lambda: batch(small, dst)),
+                                                  "parent_loop": kernel_ms(lambda: loop(small, dst))},
+                        "kernels_all_tensors": {"batch": kernel_ms(lambda: batch(inflated, dst))}}
+    print(json.dumps({"metric": "ms, RoundEnd.ingest of one lossy-coded upload (batched inflate) against the per-tensor loop",
+                      "workload": args.workload, "windows": WINDOWS, "steps_per_window": args.ingest_steps,
+                      "pipelines": result}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="resnet50_fp32")
@@ -39,7 +135,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--ingest-steps", type=int, default=3)
+    ap.add_argument("--lossy-ingest", action="store_true", help="only the KC / SKC / STC ingest A/B")
     args = ap.parse_args()
+    if args.lossy_ingest:
+        return lossy_ingest(args)
 
     import torch
     from openfl_amd import _lib
