@@ -99,7 +99,13 @@ class LabelTable:
     def from_rules(cls, starts, ends, mids, values, device):
         """Records built on the host (one H2D): tensor t = arena elements
         [starts[t], ends[t]), labelled values[t][j] for the first j with
-        x <= mids[t][j] (mids, values: [T, 8] float32)."""
+        x <= mids[t][j] (mids, values: [T, 8] float32) -- j = the number of
+        mids[t][:7] below x, so a NaN takes index 0.  mids[t] is
+        non-decreasing and mids[t][7] = +inf, as in the records k_bkm_tab and
+        ternary_label_table write.  label_apply accepts empty records
+        (start == end); gzip_ranks(label=) takes non-empty ascending ones.
+        Held to NumPy on designed rules by tests/test_gpu_label_designed.py
+        (cases: tests/label_cases.py)."""
         T = len(starts)
         rec = np.zeros(T, np.dtype([("start", "<i8"), ("end", "<i8"), ("mid", "<f4", 8), ("rank", "<f4", 8)]))
         assert rec.dtype.itemsize == cls.REC_BYTES

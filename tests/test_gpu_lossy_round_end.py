@@ -7,7 +7,11 @@ reference's per-tensor sequence (aggregator.py:780-865: aggregate ->
 generate_delta -> compress -> decompress -> apply_delta) run with the same
 openfl_amd pipeline object through TensorCodec.  Everything is compared bit
 for bit; payloads that the host gzip made (tensors of fewer than n_clusters
-elements; the gzip header carries a time stamp) by their decompressed bytes."""
+elements; the gzip header carries a time stamp) by their decompressed bytes.
+
+The test_label_apply_* tests here compare ofl_label_apply with its sibling
+kernels on one fit of random data; test_gpu_label_designed.py holds it to NumPy
+on the designed rules and layouts of tests/label_cases.py."""
 import gzip
 
 import numpy as np
