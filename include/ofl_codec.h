@@ -572,6 +572,28 @@ typedef struct {
 int ofl_adaptive_step(int ncollab, const float* const* xs, const float* weights, const float* base, int64_t n,
                       float* p, float* m, float* v, const ofl_adaptive_consts* k, float* agg_out, float* delta_out,
                       void* stream);
+/* The same step one collaborator at a time (core/adaptive_aggregation.py:38-113:
+ * _make_gradient's sum() needs no two collaborators together; utilities/
+ * optimizers/numpy/{adam,yogi,adagrad}_optimizer.py for the update):
+ * ofl_adaptive_step's sequence of roundings per element, so the same bits,
+ * with one float32 gradient arena resident instead of every collaborator,
+ * and no limit on their number.
+ * ofl_adaptive_accumulate  t = w * (base - x); first != 0: g = +0.0f + t (the
+ *                 add is kept: a -0.0 product becomes +0.0, as sum() from 0
+ *                 makes it); otherwise g = g + t.  w: already rounded to
+ *                 float32.  Call in the collaborators' order.  Reads 8 (then
+ *                 12) and writes 4 bytes per element; x with non-temporal loads.
+ * ofl_adaptive_finish  ofl_adaptive_step from the gradient on: the kind's update
+ *                 of p, m, v in place from g (m is not touched by ADAGRAD and
+ *                 may be NULL there), agg_out = p after the step, delta_out = p
+ *                 after the step - base (either may be NULL, either may be g
+ *                 itself).  g, base, p, v (and m) are required.  Reads 20
+ *                 (ADAGRAD 16) and writes 12 to 20 bytes per element.
+ * Both: 16-byte vector body when every pointer is 16-byte aligned, else
+ * scalar; one launch, async. */
+int ofl_adaptive_accumulate(const float* x, float w, const float* base, int first, int64_t n, float* g, void* stream);
+int ofl_adaptive_finish(const float* g, const float* base, int64_t n, float* p, float* m, float* v,
+                        const ofl_adaptive_consts* k, float* agg_out, float* delta_out, void* stream);
 
 /* ---- gzip of rank arrays (csrc/deflate_kernels.hip) -------------------------
  * GZIPTransformer.forward (kc_pipeline.py:128-141, skc_pipeline.py:201-215,

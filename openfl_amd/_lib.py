@@ -34,7 +34,7 @@ EXPORTS = (
     "ofl_wavg_points_workspace_bytes", "ofl_wavg_delta_points", "ofl_apply_delta",
     "ofl_apply_delta_ranges", "ofl_wavg_delta32_ranges", "ofl_sub_f32_f64",
     "ofl_median_delta", "ofl_gmedian_workspace_bytes", "ofl_gmedian_delta", "ofl_agg_delta_seeds",
-    "ofl_adaptive_step",
+    "ofl_adaptive_step", "ofl_adaptive_accumulate", "ofl_adaptive_finish",
     "ofl_gzip_last_error", "ofl_gzip_ranks_workspace_bytes", "ofl_gzip_ranks_bound", "ofl_gzip_ranks", "ofl_gzip_ranks_to", "ofl_gzip_label_to", "ofl_side_stream",
     "ofl_gzip_ranks_batch_workspace_bytes", "ofl_gzip_ranks_batch_bound", "ofl_gzip_ranks_batch",
     "ofl_gunzip_members", "ofl_gzip_member_index", "ofl_inflate_members", "ofl_inflate_tlz_workspace_bytes",
@@ -191,6 +191,10 @@ def _bind(L):
     L.ofl_agg_delta_seeds.restype = i32
     L.ofl_adaptive_step.argtypes = [i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.ofl_adaptive_step.restype = i32
+    L.ofl_adaptive_accumulate.argtypes = [vp, ctypes.c_float, vp, i32, i64, vp, vp]
+    L.ofl_adaptive_accumulate.restype = i32
+    L.ofl_adaptive_finish.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.ofl_adaptive_finish.restype = i32
     L.ofl_gzip_last_error.restype = ctypes.c_char_p
     L.ofl_gzip_ranks_workspace_bytes.argtypes = [i64]
     L.ofl_gzip_ranks_workspace_bytes.restype = sz

@@ -33,7 +33,10 @@ RoundEnd.ingest takes one collaborator's upload (payload bytes + metadata per
 tensor, as the aggregator receives them) to a device arena, and
 RoundEnd.accumulator / finish take the weighted average one collaborator at
 a time (ofl_wavg_accumulate, ofl_wavg_finish) with run()'s results bit for
-bit (tests/test_gpu_round_ingest.py, test_gpu_round_stream.py).
+bit (DESIGN.md 3.11, tests/test_gpu_round_ingest.py, test_gpu_round_stream.py);
+for the FedOpt optimisers they take the gradient one collaborator at a time
+(ofl_adaptive_accumulate, ofl_adaptive_finish; DESIGN.md 3.8,
+tests/test_gpu_adaptive_stream.py).
 
 Beside the weighted average: Median and GeometricMedian, and the FedOpt
 server optimisers AdamAdaptiveAggregation, YogiAdaptiveAggregation and
@@ -386,6 +389,25 @@ def adaptive_step(hyper, steps_taken, xs, weights32, base, n, p, m, v, agg_out=N
         ctypes.addressof(k), _ptr(agg_out), _ptr(delta_out), _stream(device)))
 
 
+def adaptive_accumulate(x, weight32, base, n, g, first, device=None):
+    """One ofl_adaptive_accumulate launch on the current stream: collaborator x
+    folded into the float32 gradient g over n elements, g = (+0.0 if first
+    else g) + weight32 * (base - x); adaptive_step's gradient chain, one link."""
+    _lib.check_agg(_lib.lib().ofl_adaptive_accumulate(x.data_ptr(), float(np.float32(weight32)), base.data_ptr(),
+                                                      1 if first else 0, int(n), g.data_ptr(), _stream(device)))
+
+
+def adaptive_finish(hyper, steps_taken, g, base, n, p, m, v, agg_out=None, delta_out=None, device=None):
+    """One ofl_adaptive_finish launch on the current stream: adaptive_step from
+    the accumulated gradient g on -- the state p, m, v updated in place (m may
+    be None for adagrad), the step after `steps_taken`; agg_out = new p and
+    delta_out = new p - base if given (either may be g)."""
+    k = hyper.consts(steps_taken)
+    _lib.check_agg(_lib.lib().ofl_adaptive_finish(
+        g.data_ptr(), base.data_ptr(), int(n), p.data_ptr(), _ptr(m), v.data_ptr(), ctypes.addressof(k),
+        _ptr(agg_out), _ptr(delta_out), _stream(device)))
+
+
 class _AdaptiveAggregation(_Plugin):
     """AdaptiveAggregation (core/adaptive_aggregation.py:16-113) with the
     optimiser's state on the device.  params: dict name -> float32 array, the
@@ -703,6 +725,52 @@ class WavgAccumulator:
         then add(that, weight): one collaborator's upload as it arrives."""
         if self.finished:
             raise _lib.CodecError("accumulator: add_upload() after finish()")
+        self._scratch = self.re.ingest(items, lossless=lossless, delta=delta, base_arena=base_arena, out=self._scratch)
+        self.add(self._scratch, weight)
+
+
+class AdaptiveAccumulator:
+    """RoundEnd.accumulator() of an "adam", "yogi" or "adagrad" RoundEnd: the
+    optimiser's gradient taken one collaborator at a time.  add(arena, weight)
+    folds one collaborator into the float32 gradient arena `sums`
+    (ofl_adaptive_accumulate: g = g + w * (base - x), from +0.0) and is done
+    with it; RoundEnd.finish takes the optimiser step from it.  The order of
+    add() is the order of the reference's sum(), so the caller adds in the
+    collaborators' order on one stream (the current one).  Any number of
+    collaborators; base: the arena every gradient term is formed against."""
+
+    def __init__(self, re, sums, base):
+        self.re = re
+        self.sums = sums
+        self.base = base
+        self.weights = []
+        self.finished = False
+        self._scratch = None   # add_upload's decode arena
+
+    def add(self, arena, weight):
+        """Fold one collaborator in: arena (this layout, float32, on the
+        device; free to reuse once the current stream has passed this call)
+        and its weight, a Python int or float or a np.float32 as run() takes
+        them."""
+        re = self.re
+        if self.finished:
+            raise _lib.CodecError("accumulator: add() after finish()")
+        re._check_arena(arena)
+        w32 = self._weight32(weight)
+        with torch.cuda.device(re.device):
+            adaptive_accumulate(arena, w32, self.base, re.arena_numel, self.sums, not self.weights, device=re.device)
+        self.weights.append(weight)
+
+    def _weight32(self, weight):
+        """_f32_weights' rule, and its errors, on the next collaborator's weight."""
+        return _f32_weights(f"{self.re.aggregation} accumulator, collaborator {len(self.weights)}", [weight])[0]
+
+    def add_upload(self, items, weight, lossless=False, delta=True, base_arena=None):
+        """re.ingest(items, ...) into this accumulator's own scratch arena,
+        then add(that, weight): one collaborator's upload as it arrives."""
+        if self.finished:
+            raise _lib.CodecError("accumulator: add_upload() after finish()")
+        self._weight32(weight)  # refused before the ingest launches anything
         self._scratch = self.re.ingest(items, lossless=lossless, delta=delta, base_arena=base_arena, out=self._scratch)
         self.add(self._scratch, weight)
 
@@ -1081,17 +1149,33 @@ class RoundEnd:
         else:
             out[:self.arena_numel].copy_(dst)
 
-    # -- the weighted average one collaborator at a time --
-    def accumulator(self, sums=None):
-        """A WavgAccumulator for one round of this layout (aggregation
-        "weighted_average" only): acc.add(arena, weight) or acc.add_upload(items,
-        weight, ...) per collaborator, in the collaborators' order, then
-        finish(acc, ...).  sums: the float64 arena (arena_numel elements) the
-        running sums and then the average live in; default: a new one."""
+    # -- the aggregate one collaborator at a time --
+    def accumulator(self, sums=None, base_arena=None):
+        """An accumulator for one round of this layout: acc.add(arena, weight)
+        or acc.add_upload(items, weight, ...) per collaborator, in the
+        collaborators' order, then finish(acc, ...).
+        aggregation "weighted_average" -> a WavgAccumulator; sums: the float64
+        arena (arena_numel elements) the running sums and then the average
+        live in; default: a new one.  base_arena is not needed before finish().
+        "adam", "yogi", "adagrad" -> an AdaptiveAccumulator; base_arena is
+        required (every add forms its gradient term against it) and
+        init_optimizer() must have been called; sums: the float32 gradient
+        arena (arena_numel elements; finish() writes the float32 delta over
+        it and the round's tail works in it); default: a new one.  The medians need every collaborator at once
+        and have none."""
         dev = resolve_device(getattr(self, "device", None))
+        if self.aggregation in ADAPTIVE_AGGREGATIONS:
+            self._adaptive_ready(base_arena)
+            self._check_arena(base_arena)
+            if sums is None:
+                sums = self._empty_arena()
+            elif not (sums.is_cuda and sums.dtype == torch.float32 and sums.is_contiguous()
+                      and sums.numel() >= self.arena_numel):
+                raise _lib.CodecError("sums must be a contiguous float32 device tensor of arena_numel elements")
+            return AdaptiveAccumulator(self, sums, base_arena)
         if self.aggregation != "weighted_average":
-            raise _lib.CodecError(f"accumulator() is the weighted average's; this RoundEnd aggregates by "
-                                  f"{self.aggregation!r}")
+            raise _lib.CodecError(f"accumulator() is the weighted average's and the optimisers'; this RoundEnd "
+                                  f"aggregates by {self.aggregation!r}")
         if sums is None:
             sums = torch.empty(self.arena_numel, dtype=torch.float64, device=dev)
         elif not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous()
@@ -1113,8 +1197,15 @@ class RoundEnd:
         geometric median takes; never fused.  agg_out (float64, arena_numel
         elements) receives the average; acc.sums holds it anyway.  An
         accumulator is finished once.  All errors are raised before anything
-        is launched or drawn from np.random."""
+        is launched or drawn from np.random.
+        An AdaptiveAccumulator ("adam", "yogi", "adagrad"): one
+        ofl_adaptive_finish takes the optimiser step from acc.sums (the state
+        moves, the step count rises by one) and writes the float32 delta over
+        it; the rest is run()'s.  base_arena: None or the arena the
+        accumulator was made with; agg_out: float32."""
         dev = resolve_device(getattr(self, "device", None))
+        if isinstance(acc, AdaptiveAccumulator) and acc.re is self:
+            return self._finish_adaptive(acc, base_arena, agg_out, payloads, out)
         if not isinstance(acc, WavgAccumulator) or acc.re is not self:
             raise _lib.CodecError("finish() takes an accumulator() of this RoundEnd")
         if acc.finished:
@@ -1145,6 +1236,29 @@ class RoundEnd:
             if agg_out is not None and agg_out.data_ptr() != acc.sums.data_ptr():
                 agg_out[:self.arena_numel].copy_(acc.sums[:self.arena_numel])
             return self._tail(delta, _AggSeeds(acc.sums, 1, base_arena), [], acc.weights, base_arena, payloads, out)
+
+    def _finish_adaptive(self, acc, base_arena, agg_out, payloads, out):
+        """finish() of an AdaptiveAccumulator: _delta_adaptive with the
+        gradient already summed, then the same tail."""
+        if acc.finished:
+            raise _lib.CodecError("accumulator: finish() after finish()")
+        if not acc.weights:
+            raise _lib.CodecError("accumulator: finish() without an add()")
+        if base_arena is not None and base_arena.data_ptr() != acc.base.data_ptr():
+            raise _lib.CodecError("finish(): base_arena is the arena the accumulator was made with (or None)")
+        if agg_out is not None and not (agg_out.is_cuda and agg_out.dtype == torch.float32
+                                        and agg_out.numel() >= self.arena_numel):
+            raise _lib.CodecError("agg_out must be float32 with arena_numel elements")
+        if out is not None:
+            self._check_arena(out)
+        acc.finished = True
+        p, m, v = self._opt
+        with torch.cuda.device(self.device):
+            delta = acc.sums[:self.arena_numel]   # in place: a lane reads its gradient before it writes its delta
+            adaptive_finish(self._hyper, self._opt_step, delta, acc.base, self.arena_numel, p, m, v,
+                            agg_out=agg_out, delta_out=delta, device=self.device)
+            self._opt_step += 1
+            return self._tail(delta, _AggSeeds(delta, 0, None), [], acc.weights, acc.base, payloads, out)
 
     # -- the optimiser's state (aggregation "adam" / "yogi" / "adagrad") --
     def init_optimizer(self, params_arena):
@@ -1270,10 +1384,7 @@ class RoundEnd:
         """one elementwise step over the whole arena (in the alignment gaps
         everything is zero: a zero gradient); the float32 delta it writes is
         generate_delta of two float32 arrays."""
-        if self._opt is None:
-            raise _lib.CodecError(f"{self.aggregation}: call init_optimizer(params_arena) before run()")
-        if base_arena is None:
-            raise _lib.CodecError(f"{self.aggregation}: base_arena is required, the gradient is formed against it")
+        self._adaptive_ready(base_arena)
         _check_collaborators(self.aggregation, len(xs), _ADAPTIVE_MAX_C)
         if weights is None or len(weights) != len(xs) or not xs:
             raise _lib.CodecError("one weight per collaborator tensor")
@@ -1284,6 +1395,12 @@ class RoundEnd:
                       delta_out=delta, device=self.device)
         self._opt_step += 1
         return delta, _AggSeeds(delta, 0, None)
+
+    def _adaptive_ready(self, base_arena):
+        if self._opt is None:
+            raise _lib.CodecError(f"{self.aggregation}: call init_optimizer(params_arena) before run()")
+        if base_arena is None:
+            raise _lib.CodecError(f"{self.aggregation}: base_arena is required, the gradient is formed against it")
 
     def _device_seeds(self, src, xs, base_arena):
         """Step 2 of run(), into self._seeds without a host round trip: serial

@@ -1276,3 +1276,191 @@ int ofl_adaptive_step(int ncollab, const float* const* xs, const float* weights,
 }
 
 }  // extern "C"
+
+// ---- the same step one collaborator at a time ------------------------------------
+// ada_elem's gradient chain needs no two collaborators together, so it runs one
+// collaborator per launch into a float32 gradient arena,
+//   first:  g = +0.0f + w * (base - x)        later:  g = g + w * (base - x)
+// (the first add is kept: a -0.0 product becomes +0.0, as the chain from +0.0f
+// makes it -- unlike k_wavg_accumulate, whose reference starts from the first
+// product), and only the state update, ada_update itself, needs p, m and v.
+// The roundings per element are k_adaptive's, so are the bits, and nothing
+// bounds the collaborator count.
+//   k_adaptive_accumulate  reads x and base (+ g after the first add), writes g:
+//                          8 + 4 bytes per element, then 12 + 4
+//   k_adaptive_finish      reads g, base, p, m, v (20; Adagrad 16), writes p, m, v
+//                          and the optional aggregate and delta (12 to 20)
+// The accumulate is three short streams with next to no arithmetic: what it
+// needs is bytes in flight.  A lane of quads_in_flight keeps Q 16-B loads of
+// every array outstanding (its quads lie one grid stride apart, so a wave's
+// loads stay contiguous) before it uses the first; the grid is sized for that.
+// The finish keeps one quad per array, as k_adaptive does: it has five streams
+// in and up to five out, and more quads made it no faster.
+
+namespace agg {
+
+// quads_then_tail with Q quads per lane per trip: quads(q, stride, Q) works on
+// the quads q, q + stride, .., q + (Q - 1) stride (quad q: elements 4q .. 4q + 3);
+// the trips that no longer fill Q take them one at a time
+template <int Q, class B, class E>
+__device__ __forceinline__ void quads_in_flight(int64_t n, int vec, B quads, E elem) {
+    const int64_t stride = (int64_t)gridDim.x * kNT;
+    const int64_t t0 = (int64_t)blockIdx.x * kNT + threadIdx.x;
+    int64_t tail = 0;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        int64_t q = t0;
+        for (; q + (Q - 1) * stride < n4; q += Q * stride) quads(q, stride, std::integral_constant<int, Q>{});
+        for (; q < n4; q += stride) quads(q, stride, std::integral_constant<int, 1>{});
+        tail = 4 * n4;
+    }
+    for (int64_t i = tail + t0; i < n; i += stride) elem(i);
+}
+
+// the two kernels' float32 operations stay single VALU operations, one rounding
+// each as written: no packed-float32 forms (v_pk_*_f32) are selected for them
+#if defined(__HIP_DEVICE_COMPILE__)
+#define OFL_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define OFL_NO_PACKED_F32
+#endif
+
+constexpr int kAdaAccQ = 8;  // quads of x, base and g in flight per lane
+
+struct AdaAccArgs {
+    const float* x;
+    const float* base;
+    float* g;
+    float w;
+    int64_t n;
+};
+
+// x is read once per round and never again: its loads are non-temporal, so
+// that the lines of g and base, which the next add reads again, are the ones
+// a cache keeps (measured: no slower at any Q, faster at 4 and 8)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 load_once(const float* p) {
+    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
+template <bool FIRST>
+__device__ __forceinline__ float ada_acc(float w, float b, float x, float g) {
+#pragma clang fp contract(off)
+    const float d = b - x;
+    const float t = w * d;
+    return (FIRST ? 0.0f : g) + t;
+}
+
+template <bool FIRST>
+__device__ __forceinline__ void ada_acc_elem(const AdaAccArgs& a, int64_t i) {
+    a.g[i] = ada_acc<FIRST>(a.w, a.base[i], a.x[i], FIRST ? 0.0f : a.g[i]);
+}
+
+// every load of the Q quads is issued before the first result is stored; a
+// lane reads its own elements of g before it writes them
+template <bool FIRST, int Q>
+__device__ __forceinline__ void ada_acc_quads(const AdaAccArgs& a, int64_t q, int64_t stride) {
+    float4 x[Q], b[Q], g[Q];
+#pragma unroll
+    for (int k = 0; k < Q; ++k) x[k] = load_once(a.x + 4 * (q + k * stride));
+#pragma unroll
+    for (int k = 0; k < Q; ++k) b[k] = *reinterpret_cast<const float4*>(a.base + 4 * (q + k * stride));
+#pragma unroll
+    for (int k = 0; k < Q; ++k)
+        g[k] = FIRST ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(a.g + 4 * (q + k * stride));
+    __builtin_amdgcn_sched_barrier(0);  // no load sinks below this line: all 3 Q are issued first
+#pragma unroll
+    for (int k = 0; k < Q; ++k)
+        *reinterpret_cast<float4*>(a.g + 4 * (q + k * stride)) =
+            make_float4(ada_acc<FIRST>(a.w, b[k].x, x[k].x, g[k].x), ada_acc<FIRST>(a.w, b[k].y, x[k].y, g[k].y),
+                        ada_acc<FIRST>(a.w, b[k].z, x[k].z, g[k].z), ada_acc<FIRST>(a.w, b[k].w, x[k].w, g[k].w));
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(kNT) OFL_NO_PACKED_F32 void k_adaptive_accumulate(AdaAccArgs a, int vec) {
+    quads_in_flight<kAdaAccQ>(
+        a.n, vec, [&](int64_t q, int64_t stride, auto Q) { ada_acc_quads<FIRST, decltype(Q)::value>(a, q, stride); },
+        [&](int64_t i) { ada_acc_elem<FIRST>(a, i); });
+}
+
+struct AdaFinArgs {
+    const float* g;
+    AdaIO io;
+    ofl_adaptive_consts k;
+};
+
+// the tail of ada_elem: the state update from a finished gradient
+__device__ __forceinline__ void ada_fin_elem(const AdaFinArgs& a, int64_t i) {
+#pragma clang fp contract(off)
+    const bool moment = a.k.kind != OFL_ADAPTIVE_ADAGRAD;
+    const float g = a.g[i], b = a.io.base[i];
+    float p = a.io.p[i], m = moment ? a.io.m[i] : 0.f, v = a.io.v[i];
+    ada_update(a.k, g, p, m, v);
+    a.io.p[i] = p;
+    if (moment) a.io.m[i] = m;
+    a.io.v[i] = v;
+    if (a.io.agg) a.io.agg[i] = p;
+    if (a.io.delta) a.io.delta[i] = p - b;
+}
+
+// the tail of ada_quad: every load, then the updates and the stores (agg or
+// delta may be g's own arena: a lane has read its g by then)
+__device__ __forceinline__ void ada_fin_quad(const AdaFinArgs& a, int64_t i) {
+#pragma clang fp contract(off)
+    const bool moment = a.k.kind != OFL_ADAPTIVE_ADAGRAD;
+    const float4 g = *reinterpret_cast<const float4*>(a.g + i);
+    float4 p = *reinterpret_cast<const float4*>(a.io.p + i);
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (moment) m = *reinterpret_cast<const float4*>(a.io.m + i);
+    float4 v = *reinterpret_cast<const float4*>(a.io.v + i);
+    const float4 b = *reinterpret_cast<const float4*>(a.io.base + i);
+    __builtin_amdgcn_sched_barrier(0);  // no load sinks below this line
+    ada_update(a.k, g.x, p.x, m.x, v.x);
+    ada_update(a.k, g.y, p.y, m.y, v.y);
+    ada_update(a.k, g.z, p.z, m.z, v.z);
+    ada_update(a.k, g.w, p.w, m.w, v.w);
+    *reinterpret_cast<float4*>(a.io.p + i) = p;
+    if (moment) *reinterpret_cast<float4*>(a.io.m + i) = m;
+    *reinterpret_cast<float4*>(a.io.v + i) = v;
+    if (a.io.agg) *reinterpret_cast<float4*>(a.io.agg + i) = p;
+    if (a.io.delta) *reinterpret_cast<float4*>(a.io.delta + i) = make_float4(p.x - b.x, p.y - b.y, p.z - b.z, p.w - b.w);
+}
+
+__global__ __launch_bounds__(kNT) OFL_NO_PACKED_F32 void k_adaptive_finish(AdaFinArgs a, int vec) {
+    quads_then_tail(a.io.n, vec, [&](int64_t i) { ada_fin_quad(a, i); }, [&](int64_t i) { ada_fin_elem(a, i); });
+}
+
+}  // namespace agg
+
+extern "C" {
+
+int ofl_adaptive_accumulate(const float* x, float w, const float* base, int first, int64_t n, float* g, void* stream) {
+    if (n < 0 || (n && (!x || !base || !g))) return afail(OFL_EINVAL, "adaptive accumulate: bad arguments");
+    if (n == 0) return OFL_OK;
+    const agg::AdaAccArgs a{x, base, g, w, n};
+    const int vec = aligned16(&x, 1, base, g);
+    const dim3 grid(grid_for(n, 4 * agg::kAdaAccQ));
+    hipLaunchKernelGGL(first ? agg::k_adaptive_accumulate<true> : agg::k_adaptive_accumulate<false>, grid,
+                       dim3(agg::kNT), 0, static_cast<hipStream_t>(stream), a, vec);
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_adaptive_finish(const float* g, const float* base, int64_t n, float* p, float* m, float* v,
+                        const ofl_adaptive_consts* k, float* agg_out, float* delta_out, void* stream) {
+    if (n < 0) return afail(OFL_EINVAL, "adaptive finish: negative size");
+    if (!k || k->kind < OFL_ADAPTIVE_ADAM || k->kind > OFL_ADAPTIVE_ADAGRAD)
+        return afail(OFL_EINVAL, "adaptive finish: kind must be OFL_ADAPTIVE_ADAM, _YOGI or _ADAGRAD");
+    if (n == 0) return OFL_OK;
+    if (!g || !base || !p || !v || (k->kind != OFL_ADAPTIVE_ADAGRAD && !m))
+        return afail(OFL_EINVAL, "adaptive finish: the gradient, base and the state arenas are required");
+    const agg::AdaFinArgs a{g, {base, p, k->kind != OFL_ADAPTIVE_ADAGRAD ? m : nullptr, v, agg_out, delta_out, n}, *k};
+    const int vec = aligned16(&g, 1, base, p, a.io.m, v, agg_out, delta_out);
+    hipLaunchKernelGGL(agg::k_adaptive_finish, dim3(grid_for(n, 4)), dim3(agg::kNT), 0,
+                       static_cast<hipStream_t>(stream), a, vec);
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+}  // extern "C"

@@ -17,6 +17,12 @@ One process, windows alternated (A B A B A B, the minimum and the spread of each
               backward_batch() + pack(), the route through host arrays.
   --lossy-ingest   instead: one KC-, SKC- and STC-coded upload, ingest()
               against the per-tensor inflate loop it replaced (lossy_ingest).
+  --aggregation adam|yogi|adagrad   instead: the FedOpt round end streamed,
+              accumulator(base_arena=) + C x add() + finish() against run() on
+              the same arenas (12 B per collaborator-element more: the base
+              read again and the float32 gradient read and written per add), and ofl_adaptive_accumulate
+              and ofl_adaptive_finish alone beside ofl_wavg_accumulate,
+              ofl_wavg_finish and k_adaptive in bytes per second (adaptive_stream).
 Prints one JSON line.
 """
 import argparse
@@ -128,6 +134,103 @@ def lossy_ingest(args):
                       "pipelines": result}), flush=True)
 
 
+def adaptive_stream(args):
+    """--aggregation: the streamed FedOpt round end against run(), and the two
+    streaming kernels beside their yardsticks, alternated windows in one process."""
+    import torch
+    from openfl_amd import _lib
+    from openfl_amd import aggregation as A
+    from openfl_amd.pipelines import EdenPipeline
+    from openfl_amd.workloads import WORKLOADS
+    dev = torch.device("cuda", 0)
+    kind = args.aggregation
+    shapes = [tuple(s) for _, s in WORKLOADS[args.workload]()]
+    pipe = EdenPipeline(n_bits=8, device=dev, seed_mode="fast")
+    re_s, re_r = (A.RoundEnd(pipe, shapes, dev, aggregation=kind) for _ in range(2))
+    C, n = args.collaborators, re_s.arena_numel
+    g = torch.Generator(device=dev)
+    arenas = []
+    for c in range(C + 1):
+        g.manual_seed(1000 + c)
+        a = torch.empty(n, dtype=torch.float32, device=dev).normal_(0.0, 0.01, generator=g)
+        re_s._zero_gaps(a)
+        arenas.append(a)
+    base, collabs = arenas[0], arenas[1:]
+    w = [float(v) for v in np.random.default_rng(0).random(C) + 0.5]
+    for re in (re_s, re_r):
+        re.init_optimizer(base)
+    out, grad = torch.empty_like(base), torch.empty_like(base)
+    np.random.seed(0)
+
+    def timed(fn, steps):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / steps
+
+    def windows(fns, steps):
+        times = {k: [] for k in fns}
+        for _ in range(WINDOWS):
+            for k, fn in fns.items():
+                times[k].append(timed(fn, steps))
+        return times
+
+    def ms(ts):
+        return {"min": round(1e3 * min(ts), 4), "max": round(1e3 * max(ts), 4)}
+
+    def stream_round():
+        acc = re_s.accumulator(sums=grad, base_arena=base)
+        for x, wc in zip(collabs, w):
+            acc.add(x, wc)
+        re_s.finish(acc, payloads=False, out=out)
+
+    t_round = windows({"streaming": stream_round,
+                       "run": lambda: re_r.run(collabs, w, base, payloads=False, out=out)}, args.steps)
+
+    # the kernels alone, by bytes moved, beside the kernels that stream the same arenas
+    L = _lib.lib()
+    st = torch.cuda.current_stream(dev).cuda_stream
+    hyper, state = re_s._hyper, re_s.optimizer_state()
+    p, m, v = state["params"], state["first_moment"], state["second_moment"]
+    delta, sums = torch.empty_like(base), torch.empty(n, dtype=torch.float64, device=dev)
+    w32 = np.asarray(w, np.float32)
+    A.adaptive_accumulate(collabs[0], w32[0], base, n, grad, True, device=dev)
+    _lib.check_agg(L.ofl_wavg_accumulate(collabs[0].data_ptr(), 1.0, 1, n, sums.data_ptr(), st))
+    sv = 4 if kind == "adagrad" else 0   # adagrad has no first moment: 4 B less each way
+    fns = {"adaptive_accumulate_first": lambda: A.adaptive_accumulate(collabs[0], w32[0], base, n, delta, True, device=dev),
+           "adaptive_accumulate": lambda: A.adaptive_accumulate(collabs[1 % C], 1e-3, base, n, grad, False, device=dev),
+           "adaptive_finish": lambda: A.adaptive_finish(hyper, 0, grad, base, n, p, m, v, delta_out=delta, device=dev),
+           "wavg_accumulate": lambda: _lib.check_agg(
+               L.ofl_wavg_accumulate(collabs[0].data_ptr(), 1.0, 0, n, sums.data_ptr(), st)),
+           "wavg_finish": lambda: _lib.check_agg(
+               L.ofl_wavg_finish(sums.data_ptr(), 1.0, base.data_ptr(), n, None, delta.data_ptr(), st)),
+           "k_adaptive": lambda: A.adaptive_step(hyper, 0, collabs, w32, base, n, p, m, v, delta_out=delta, device=dev)}
+    moved = {"adaptive_accumulate_first": 12 * n, "adaptive_accumulate": 16 * n, "adaptive_finish": (36 - 2 * sv) * n,
+             "wavg_accumulate": 20 * n, "wavg_finish": 24 * n, "k_adaptive": (4 * C + 32 - 2 * sv) * n}
+    t_k = windows(fns, max(args.steps, 20))
+    kernels = {k: {"ms": ms(ts), "bytes_moved": moved[k], "GBps_at_min": round(moved[k] / min(ts) / 1e9, 1),
+                   "GBps_at_max": round(moved[k] / max(ts) / 1e9, 1),
+                   "frac_of_peak_hbm": round(moved[k] / min(ts) / 1e9 / PEAK_HBM_GBPS, 4)} for k, ts in t_k.items()}
+    nbytes = 4 * sum(re_s.numels)
+    t = min(t_round["streaming"])
+    print(json.dumps({
+        "metric": f"GiB/s aggregator round end, {kind} server optimiser, collaborators accumulated one at a time "
+                  "(accumulator + C x add + finish: Eden encode/decode + apply), device-resident",
+        "value": round(nbytes / t / 2 ** 30, 3), "unit": "GiB/s", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms(t_round["streaming"]), "higher_is_better": True, "dtype": "f32",
+        "data": "synthetic N(0, 0.01^2) updates and base, resident in HBM",
+        "config": {"workload": args.workload, "tensors": len(shapes), "bytes": nbytes, "collaborators": C,
+                   "aggregation": kind, "n_bits": 8, "seed_mode": "fast", "windows": WINDOWS},
+        "also": {"run_same_interleave": {"ms_per_step": ms(t_round["run"])},
+                 "extra_bytes_streaming": (12 * C - 4) * n,
+                 "resident_arena_bytes": {"run": 4 * n * (C + 6 - sv // 4), "streaming": 4 * n * (7 - sv // 4)},
+                 "kernels": kernels}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="resnet50_fp32")
@@ -136,9 +239,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--ingest-steps", type=int, default=3)
     ap.add_argument("--lossy-ingest", action="store_true", help="only the KC / SKC / STC ingest A/B")
+    ap.add_argument("--aggregation", choices=("adam", "yogi", "adagrad"), help="only the streamed FedOpt round end A/B")
     args = ap.parse_args()
     if args.lossy_ingest:
         return lossy_ingest(args)
+    if args.aggregation:
+        return adaptive_stream(args)
 
     import torch
     from openfl_amd import _lib
