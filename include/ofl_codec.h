@@ -176,6 +176,29 @@ int ofl_eden_encode_wavg(ofl_eden_plan_t plan, const float* const* collab_arenas
 int ofl_eden_decode_add(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uint32_t* seeds,
                         const float* scales, const float* base_arena, float* y_arena, void* ws,
                         size_t ws_bytes, void* stream);
+/* The round trip y = decode(encode(x)) (+ base when given) with the bytes
+ * discarded: what Aggregator._prepare_trained computes when nothing is sent
+ * (aggregator.py:816-826), and the y of a collaborator's error feedback
+ * (residual = x - y).  y_arena and scales_out hold exactly what
+ * ofl_eden_encode followed by ofl_eden_decode_add would leave there, but the
+ * slices above 2^15 elements never make their bit planes: encode's last row
+ * pass and decode's first are one kernel (k_rt_row) that replaces each value
+ * by its centroid in registers, and a wave's decode passes follow its encode
+ * passes on the wave's stream.  Slices of at most 2^15 elements run their
+ * encode and decode launches through a plane scratch inside ws.
+ * ws: DEVICE, ofl_eden_roundtrip_workspace_bytes() bytes (-1: null plan).
+ * y_arena may alias base and may alias x_arena.  roundtrip_wavg: the first
+ * row pass is ofl_eden_encode_wavg's (same collaborator, weight, base_arena
+ * and delta_arena arguments); `base`, nullable, is what is added to y.
+ * Null x / seeds / y / scales, or bad wavg arguments: OFL_EINVAL, nothing
+ * launched. */
+int64_t ofl_eden_roundtrip_workspace_bytes(ofl_eden_plan_t plan);
+int ofl_eden_roundtrip(ofl_eden_plan_t plan, const float* x_arena, const uint32_t* seeds, float* y_arena,
+                       float* scales_out, const float* base, void* ws, size_t ws_bytes, void* stream);
+int ofl_eden_roundtrip_wavg(ofl_eden_plan_t plan, const float* const* collab_arenas, const double* weights,
+                            int ncollab, double wsum, const float* base_arena, const float* delta_arena,
+                            const uint32_t* seeds, float* y_arena, float* scales_out, const float* base, void* ws,
+                            size_t ws_bytes, void* stream);
 
 /* The one-tensor plugin path (Eden.compress / Eden.decompress,
  * eden_pipeline.py:555-659, one tensor per TensorCodec call) in one native
@@ -248,7 +271,9 @@ int ofl_side_stream(int index, void** stream);
  * milliseconds (launch order) and the call count, and drops the records.
  * launch_info() names launch idx (kernel symbol as rocprofv3 shows it) with
  * its grid size, the bytes it reads+writes in HBM and its share of the
- * algorithmic bytes (input/output fp32 + bit planes; FWHT intermediates 0). */
+ * algorithmic bytes (input/output fp32 + bit planes; FWHT intermediates 0).
+ * `encode` names the launch list in all four calls below: 0 decode, 1 encode,
+ * 2 the round trip (ofl_eden_roundtrip). */
 int ofl_eden_plan_profile(ofl_eden_plan_t plan, int enable);
 int ofl_eden_plan_num_launches(ofl_eden_plan_t plan, int encode);
 int ofl_eden_plan_launch_info(ofl_eden_plan_t plan, int encode, int idx, char* name, int cap,

@@ -92,6 +92,7 @@ class EdenPlan:
         self.n_slices = int(L.ofl_eden_plan_num_slices(h))
         self.planes_bytes = int(L.ofl_eden_plan_planes_bytes(h))
         self.ws_bytes = int(L.ofl_eden_plan_workspace_bytes(h))
+        self.roundtrip_ws_bytes = int(L.ofl_eden_roundtrip_workspace_bytes(h))
         self.planes_offsets, self.planes_nbytes, self.first_slice, self.dims = [], [], [], []
         for t in range(nt):
             po, pb = ctypes.c_int64(), ctypes.c_int64()
@@ -145,6 +146,23 @@ class EdenPlan:
                                                y_arena.data_ptr(), ws.data_ptr() if ws is not None else None,
                                                ws.numel() if ws is not None else 0, st.cuda_stream))
 
+    def roundtrip(self, x_arena, seeds, y_arena, scales, ws, stream=None, base=None):
+        """y_arena = decode(encode(x_arena)) (+ base when given) and the
+        encode's scales, bit for bit, without the planes
+        (ofl_eden_roundtrip): ws holds roundtrip_ws_bytes; y_arena may be
+        x_arena or base."""
+        self._check(x_arena, torch.float32, self.arena_numel)
+        self._check(y_arena, torch.float32, self.arena_numel)
+        self._check(scales, torch.float32, self.n_slices)
+        self._check(seeds, torch.int32, len(self.numels))
+        if base is not None:
+            self._check(base, torch.float32, self.arena_numel)
+        st = stream if stream is not None else torch.cuda.current_stream(x_arena.device)
+        _lib.check(self._L.ofl_eden_roundtrip(self._h, x_arena.data_ptr(), seeds.data_ptr(), y_arena.data_ptr(),
+                                              scales.data_ptr(), base.data_ptr() if base is not None else None,
+                                              ws.data_ptr() if ws is not None else None,
+                                              ws.numel() if ws is not None else 0, st.cuda_stream))
+
     # -- profiling (HIP events between launches; see ofl_codec.h) --
     def profile(self, enable=True):
         _lib.check(self._L.ofl_eden_plan_profile(self._h, 1 if enable else 0))
@@ -155,15 +173,22 @@ class EdenPlan:
         ofl_eden_plan_launch_detail reports -- expl (over an explicit tile
         list: a sub-wave of a split 5-pass slice), paired (that row launch
         walks the paired tile table) and grid (workgroups launched)."""
+        return self._launches(1 if encode else 0)
+
+    def roundtrip_launches(self):
+        """The launches of a plain round trip, as launches() reports them."""
+        return self._launches(2)
+
+    def _launches(self, which):
         out = []
-        for i in range(self._L.ofl_eden_plan_num_launches(self._h, 1 if encode else 0)):
+        for i in range(self._L.ofl_eden_plan_num_launches(self._h, which)):
             name = ctypes.create_string_buffer(128)
             blocks, mv, al = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-            _lib.check(self._L.ofl_eden_plan_launch_info(self._h, 1 if encode else 0, i, name, 128,
+            _lib.check(self._L.ofl_eden_plan_launch_info(self._h, which, i, name, 128,
                                                          ctypes.byref(blocks), ctypes.byref(mv),
                                                          ctypes.byref(al)))
             expl, paired, grid = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
-            _lib.check(self._L.ofl_eden_plan_launch_detail(self._h, 1 if encode else 0, i, ctypes.byref(expl),
+            _lib.check(self._L.ofl_eden_plan_launch_detail(self._h, which, i, ctypes.byref(expl),
                                                            ctypes.byref(paired), ctypes.byref(grid)))
             out.append({"name": name.value.decode(), "blocks": blocks.value,
                         "bytes_moved": mv.value, "bytes_alg": al.value,
@@ -171,11 +196,13 @@ class EdenPlan:
         return out
 
     def profile_collect(self, encode):
-        """-> (per-launch summed ms, number of recorded calls)."""
-        n = self._L.ofl_eden_plan_num_launches(self._h, 1 if encode else 0)
+        """-> (per-launch summed ms, number of recorded calls).  encode: False
+        / True, or 2 for the round trip's launches."""
+        which = 2 if encode == 2 else 1 if encode else 0
+        n = self._L.ofl_eden_plan_num_launches(self._h, which)
         ms = np.zeros(max(n, 1), np.float64)
         calls = ctypes.c_int()
-        _lib.check(self._L.ofl_eden_plan_profile_collect(self._h, 1 if encode else 0, _ptr(ms), n,
+        _lib.check(self._L.ofl_eden_plan_profile_collect(self._h, which, _ptr(ms), n,
                                                          ctypes.byref(calls)))
         return ms[:n], calls.value
 
@@ -400,3 +427,13 @@ class EdenCodec:
         ws = self.ws.get(plan.ws_bytes, self.device)
         plan.decode(planes, seeds_dev, scales, y, ws, stream)
         return y
+
+    def roundtrip_arena(self, plan, x_arena, seeds_dev, out=None, base=None):
+        """-> (y, scales): decode_arena(encode_arena(x_arena)), + base when
+        given, in one call that makes no planes (EdenPlan.roundtrip)."""
+        y = out if out is not None else torch.empty(max(plan.arena_numel, 1), dtype=torch.float32,
+                                                    device=self.device)
+        scales = torch.empty(max(plan.n_slices, 1), dtype=torch.float32, device=self.device)
+        ws = self.ws.get(plan.roundtrip_ws_bytes, self.device)
+        plan.roundtrip(x_arena, seeds_dev, y, scales, ws, base=base)
+        return y, scales

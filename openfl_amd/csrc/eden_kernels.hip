@@ -54,6 +54,7 @@
 
 #include "eden_desc.h"
 #include "eden_plan.h"
+#include "eden_rt_plan.h"
 #include "eden_tables.h"
 #include "lds_exchange.h"
 #include "ofl_codec.h"
@@ -2304,6 +2305,9 @@ __global__ __launch_bounds__(256) void k_finalize(KArgs a) {
     }
 }
 
+// the round trip's row pass (k_rt_row), after every kernel above
+#include "eden_rt_row.h"
+
 }  // namespace ofl
 
 // ===========================================================================
@@ -2325,11 +2329,14 @@ using eden::Launch;
 
 struct ofl_eden_plan {
     eden::Plan p;               // the layout, the knobs and the schedule (host only: eden_plan.h)
+    eden::RoundTrip rt;         // the round trip's schedule, rebuilt with p's (eden_rt_plan.h)
+    const char* rt_err = nullptr;  // why the plan has none (ofl_eden_roundtrip reports it)
     // profiling: events around every launch of every call while enabled
     bool prof = false;
-    std::vector<std::vector<hipEvent_t>> prof_ev[2];  // [dec, enc][call][launch+1]
+    std::vector<std::vector<hipEvent_t>> prof_ev[3];  // [dec, enc, round trip][call][launch+1]
     std::vector<hipEvent_t> ev_pool;
     ofl::SliceDesc* d_slices = nullptr;
+    ofl::SliceDesc* d_rt_slices = nullptr;  // rt.slices
     int32_t* d_ints = nullptr;
     int device = -1;
     int ncu = 256;              // persistent row launches: one block per CU (eden::resolve)
@@ -2407,19 +2414,48 @@ constexpr bool kernels_in_enum_order() {
 static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == eden::KERNEL_COUNT && kernels_in_enum_order(),
               "kKernels: one entry per eden::KernelId, in the enum's order");
 
+// the round trip's own kernels, one entry per eden::RtKernelId
+constexpr KernelEntry kRtKernels[eden::RT_KERNEL_COUNT] = {
+    {eden::KERNEL_COUNT, ofl::k_rt_row, ofl::kRowNT, ofl::kRowC2Smem},
+};
+
 hipError_t set_all_attrs() {
-    for (const KernelEntry& k : kKernels) {
-        if (k.lds == 0) continue;
-        const hipError_t e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
-        if (e != hipSuccess) return e;
-    }
+    for (const KernelEntry* tab : {kKernels, kRtKernels})
+        for (int i = 0; i < (tab == kKernels ? (int)eden::KERNEL_COUNT : (int)eden::RT_KERNEL_COUNT); ++i) {
+            const KernelEntry& k = tab[i];
+            if (k.lds == 0) continue;
+            const hipError_t e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+            if (e != hipSuccess) return e;
+        }
     return hipSuccess;
 }
 
-int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller) {
+// which of a plan's launch lists a call runs (the ABI's `encode` argument)
+enum { RUN_DEC = 0, RUN_ENC = 1, RUN_RT = 2 };
+int num_launches(const ofl_eden_plan* pl, int which) {
+    return (int)(which == RUN_RT ? pl->rt.list.size() : which == RUN_ENC ? pl->p.enc.size() : pl->p.dec.size());
+}
+// launch idx of a list and what it runs (ncu CUs; wavg: the weighted-average
+// first pass; planes8: eden::resolve).  rt: k_rt_row, else kKernels[r.id]
+const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, bool wavg, bool planes8, const Launch*& l,
+                       eden::Resolved& r, bool& rt) {
+    rt = false;
+    if (which == RUN_RT) {
+        eden::RtResolved x;
+        l = &pl->rt.list[idx].l;
+        const char* err = eden::rt_resolve(pl->p, pl->rt.list[idx], ncu, wavg, x);
+        r = x.r;
+        rt = x.rt;
+        return err;
+    }
+    l = &(which == RUN_ENC ? pl->p.enc : pl->p.dec)[idx];
+    return eden::resolve(pl->p, *l, which == RUN_ENC, ncu, wavg, planes8, r);
+}
+
+int run(ofl_eden_plan* pl, int which, const ofl::KArgs& base, hipStream_t caller) {
     const hipError_t attrs_err = ofl_util::per_device_once([] { return set_all_attrs(); });
     if (attrs_err != hipSuccess) return fail(OFL_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(attrs_err));
-    const std::vector<Launch>& L = enc ? pl->p.enc : pl->p.dec;
+    const size_t nl = (size_t)num_launches(pl, which);
     // waves on the side stream fork from and join back into the caller's stream
     const bool two = pl->side != nullptr && !pl->p.single;
     std::unique_lock<std::mutex> lk(pl->run_mu, std::defer_lock);
@@ -2433,9 +2469,9 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
     std::vector<hipEvent_t>* evs = nullptr;
     if (pl->prof) {  // one event before and one after every launch, on its stream
         std::lock_guard<std::mutex> g(pl->mu);
-        pl->prof_ev[enc].emplace_back();
-        evs = &pl->prof_ev[enc].back();
-        for (size_t i = 0; i < 2 * L.size(); ++i) {
+        pl->prof_ev[which].emplace_back();
+        evs = &pl->prof_ev[which].back();
+        for (size_t i = 0; i < 2 * nl; ++i) {
             hipEvent_t e;
             if (!pl->ev_pool.empty()) { e = pl->ev_pool.back(); pl->ev_pool.pop_back(); }
             else HIP_TRY(hipEventCreate(&e));
@@ -2445,11 +2481,13 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
     // the two facts of the call that choose among a launch's kernels
     const bool wavg = base.wx != nullptr;
     const bool planes8 = (reinterpret_cast<uintptr_t>(base.pin) & 7u) == 0;
-    for (size_t li = 0; li < L.size(); ++li) {
-        const Launch& l = L[li];
+    for (size_t li = 0; li < nl; ++li) {
+        const Launch* lp = nullptr;
         eden::Resolved r;
-        if (const char* err = eden::resolve(pl->p, l, enc, pl->ncu, wavg, planes8, r)) return fail(OFL_EINVAL, err);
-        const KernelEntry& k = kKernels[r.id];
+        bool rt = false;
+        if (const char* err = resolve_at(pl, which, (int)li, pl->ncu, wavg, planes8, lp, r, rt)) return fail(OFL_EINVAL, err);
+        const Launch& l = *lp;
+        const KernelEntry& k = rt ? kRtKernels[eden::RT_ROW] : kKernels[r.id];
         const hipStream_t st = streams[l.stream];
         ofl::KArgs a = base;
         a.list = pl->d_ints + l.list_off;
@@ -2459,6 +2497,9 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
         a.lo = l.lo;
         a.do_nu = l.nu;
         a.npair = r.npair;
+        // the round trip has no planes of large slices for k_finalize to clear
+        // (a NaN scale is stored as 0, and decode multiplies by it)
+        if (which == RUN_RT && l.kind == eden::K_FINAL) a.nbits = 0;
         if (l.sset_off >= 0) {  // K_COLMSET
             a.sset = pl->d_ints + l.sset_off;
             a.sset_first = (int32_t)l.sset_groups;
@@ -2482,6 +2523,11 @@ int run(ofl_eden_plan* pl, bool enc, const ofl::KArgs& base, hipStream_t caller)
     return OFL_OK;
 }
 
+void build_schedules(ofl_eden_plan* pl) {
+    eden::build_schedule(pl->p, eden::kScheduleNcu);
+    pl->rt_err = eden::build_roundtrip(pl->p, pl->rt);
+}
+
 int64_t env_i64(const char* name, int64_t dflt) {
     const char* s = getenv(name);
     return (s && *s) ? strtoll(s, nullptr, 10) : dflt;
@@ -2496,7 +2542,7 @@ int set_knob(ofl_eden_plan_t pl, const char* what, const std::string& range_err,
     std::lock_guard<std::mutex> g(pl->mu);
     if (pl->uploaded) return fail(OFL_EINVAL, std::string(what) + " must be set before the plan's first encode/decode");
     assign(pl->p);
-    eden::build_schedule(pl->p, eden::kScheduleNcu);
+    build_schedules(pl);
     return OFL_OK;
 }
 int set_mode(ofl_eden_plan_t pl, const char* what, const char* minus_one, int eden::Plan::*knob, int mode) {
@@ -2557,7 +2603,7 @@ int ofl_eden_plan_create(int ntensors, const int64_t* numel, const int64_t* elem
     // default schedule (tuning overrides: OFL_EDEN_WAVE_MIB, OFL_EDEN_STREAMS)
     pl->p.wave_bytes = std::max<int64_t>(0, env_i64("OFL_EDEN_WAVE_MIB", eden::kDefaultWaveMiB)) << 20;
     pl->p.nstreams = (int)std::min<int64_t>(2, std::max<int64_t>(1, env_i64("OFL_EDEN_STREAMS", eden::kDefaultStreams)));
-    eden::build_schedule(pl->p, eden::kScheduleNcu);
+    build_schedules(pl);
     *plan_out = pl;
     return OFL_OK;
 }
@@ -2603,6 +2649,10 @@ static int ensure_device(ofl_eden_plan_t pl) {
     if (!pl->p.slices.empty()) {
         HIP_TRY(hipMalloc(&pl->d_slices, sizeof(ofl::SliceDesc) * pl->p.slices.size()));
         HIP_TRY(hipMemcpy(pl->d_slices, pl->p.slices.data(), sizeof(ofl::SliceDesc) * pl->p.slices.size(), hipMemcpyHostToDevice));
+        if (!pl->rt_err) {
+            HIP_TRY(hipMalloc(&pl->d_rt_slices, sizeof(ofl::SliceDesc) * pl->rt.slices.size()));
+            HIP_TRY(hipMemcpy(pl->d_rt_slices, pl->rt.slices.data(), sizeof(ofl::SliceDesc) * pl->rt.slices.size(), hipMemcpyHostToDevice));
+        }
     }
     if (!pl->p.ints.empty()) {
         HIP_TRY(hipMalloc(&pl->d_ints, sizeof(int32_t) * pl->p.ints.size()));
@@ -2639,6 +2689,7 @@ void ofl_eden_plan_destroy(ofl_eden_plan_t pl) {
     ofl_eden_plan_profile(pl, 0);
     for (hipEvent_t e : pl->ev_pool) (void)hipEventDestroy(e);
     if (pl->d_slices) (void)hipFree(pl->d_slices);
+    if (pl->d_rt_slices) (void)hipFree(pl->d_rt_slices);
     if (pl->d_ints) (void)hipFree(pl->d_ints);
     if (pl->ev_join2) (void)hipEventDestroy(pl->ev_join2);
     if (pl->ev_fork) (void)hipEventDestroy(pl->ev_fork);
@@ -2690,9 +2741,9 @@ int ofl_eden_plan_tensor_dims(ofl_eden_plan_t pl, int t, int64_t* dims_out) {
     return OFL_OK;
 }
 
-static int prep_args(ofl_eden_plan_t pl, ofl::KArgs& a, void* ws, size_t ws_bytes) {
+static int prep_args(ofl_eden_plan_t pl, ofl::KArgs& a, void* ws, size_t ws_bytes, bool roundtrip = false) {
     if (int rc = ensure_device(pl)) return rc;
-    const int64_t need = ofl_eden_plan_workspace_bytes(pl);
+    const int64_t need = roundtrip ? ofl_eden_roundtrip_workspace_bytes(pl) : ofl_eden_plan_workspace_bytes(pl);
     if ((int64_t)ws_bytes < need || (need > 256 && !ws)) return fail(OFL_ESPACE, "workspace too small");
     auto al = [](int64_t b) { return (b + 255) & ~255ll; };
     char* w = static_cast<char*>(ws);
@@ -2715,7 +2766,7 @@ int ofl_eden_encode(ofl_eden_plan_t pl, const float* x_arena, const uint32_t* se
     a.pout = planes_arena;
     a.seeds = seeds;
     a.scales = scales;
-    return run(pl, true, a, static_cast<hipStream_t>(stream));
+    return run(pl, RUN_ENC, a, static_cast<hipStream_t>(stream));
 }
 
 int ofl_eden_encode_wavg(ofl_eden_plan_t pl, const float* const* collab_arenas, const double* weights, int ncollab,
@@ -2736,7 +2787,7 @@ int ofl_eden_encode_wavg(ofl_eden_plan_t pl, const float* const* collab_arenas, 
     a.wc = ncollab;
     a.wsum = wsum;
     a.wbase = base_arena;
-    return run(pl, true, a, static_cast<hipStream_t>(stream));
+    return run(pl, RUN_ENC, a, static_cast<hipStream_t>(stream));
 }
 
 int ofl_eden_decode(ofl_eden_plan_t pl, const uint8_t* planes_arena, const uint32_t* seeds, const float* scales,
@@ -2755,7 +2806,58 @@ int ofl_eden_decode_add(ofl_eden_plan_t pl, const uint8_t* planes_arena, const u
     a.yadd = base_arena;
     a.seeds = seeds;
     a.scales_in = scales;
-    return run(pl, false, a, static_cast<hipStream_t>(stream));
+    return run(pl, RUN_DEC, a, static_cast<hipStream_t>(stream));
+}
+
+int64_t ofl_eden_roundtrip_workspace_bytes(ofl_eden_plan_t pl) {
+    return pl && !pl->rt_err ? eden::rt_workspace_bytes(pl->p, pl->rt) : -1;
+}
+
+// the round trip after its checks: the plan's regions of ws, the small
+// slices' planes in the scratch behind them, scales written and read back
+static int roundtrip_run(ofl_eden_plan_t pl, ofl::KArgs& a, const float* x_arena, const uint32_t* seeds, float* y_arena,
+                         float* scales_out, const float* base, void* ws, size_t ws_bytes, void* stream) {
+    if (!x_arena || !seeds || !y_arena || !scales_out) return fail(OFL_EINVAL, "roundtrip: null argument");
+    const ofl::KArgs w = a;  // the weighted-average arguments
+    if (int rc = prep_args(pl, a, ws, ws_bytes, true)) return rc;
+    a.wx = w.wx; a.ww = w.ww; a.wc = w.wc; a.wsum = w.wsum; a.wbase = w.wbase;
+    a.d = pl->d_rt_slices;
+    a.xin = x_arena;
+    a.xout = y_arena;
+    a.yadd = base;
+    a.seeds = seeds;
+    a.scales = scales_out;
+    a.scales_in = scales_out;
+    a.pout = static_cast<uint8_t*>(ws) + eden::rt_scratch_off(pl->p);
+    a.pin = a.pout;
+    return run(pl, RUN_RT, a, static_cast<hipStream_t>(stream));
+}
+
+int ofl_eden_roundtrip(ofl_eden_plan_t pl, const float* x_arena, const uint32_t* seeds, float* y_arena,
+                       float* scales_out, const float* base, void* ws, size_t ws_bytes, void* stream) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    if (pl->rt_err) return fail(OFL_EINVAL, pl->rt_err);
+    ofl::KArgs a;
+    memset(&a, 0, sizeof(a));
+    return roundtrip_run(pl, a, x_arena, seeds, y_arena, scales_out, base, ws, ws_bytes, stream);
+}
+
+int ofl_eden_roundtrip_wavg(ofl_eden_plan_t pl, const float* const* collab_arenas, const double* weights, int ncollab,
+                            double wsum, const float* base_arena, const float* delta_arena, const uint32_t* seeds,
+                            float* y_arena, float* scales_out, const float* base, void* ws, size_t ws_bytes,
+                            void* stream) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    if (pl->rt_err) return fail(OFL_EINVAL, pl->rt_err);
+    if (!collab_arenas || !weights || ncollab < 1 || ncollab > 16 || !(wsum != 0.0))
+        return fail(OFL_EINVAL, "roundtrip_wavg: 1..16 collaborators, their weights and a nonzero weight sum");
+    ofl::KArgs a;
+    memset(&a, 0, sizeof(a));
+    a.wx = collab_arenas;
+    a.ww = weights;
+    a.wc = ncollab;
+    a.wsum = wsum;
+    a.wbase = base_arena;
+    return roundtrip_run(pl, a, delta_arena, seeds, y_arena, scales_out, base, ws, ws_bytes, stream);
 }
 
 int ofl_eden_encode_host(ofl_eden_plan_t pl, const void* in_host, void* in_dev, size_t in_bytes, size_t off_seeds,
@@ -2973,7 +3075,7 @@ int ofl_copy_h2d_staged(void* dst_dev, const void* src_host, size_t bytes, int n
 int ofl_eden_plan_profile(ofl_eden_plan_t pl, int enable) {
     if (!pl) return fail(OFL_EINVAL, "null plan");
     std::lock_guard<std::mutex> g(pl->mu);
-    for (int d = 0; d < 2; ++d) {
+    for (int d = 0; d < 3; ++d) {
         for (auto& call : pl->prof_ev[d]) pl->ev_pool.insert(pl->ev_pool.end(), call.begin(), call.end());
         pl->prof_ev[d].clear();
     }
@@ -2982,18 +3084,16 @@ int ofl_eden_plan_profile(ofl_eden_plan_t pl, int enable) {
 }
 
 int ofl_eden_plan_num_launches(ofl_eden_plan_t pl, int encode) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
-    return (int)(encode ? pl->p.enc.size() : pl->p.dec.size());
+    if (!pl || encode < 0 || encode > 2) return fail(OFL_EINVAL, "null plan or unknown launch list");
+    return num_launches(pl, encode);
 }
 
 // What a launch of a plain encode / decode (no weighted average, aligned
 // planes) resolves to on the plan's device (256 CUs before its first use)
-static int resolve_plain(ofl_eden_plan_t pl, int encode, int idx, const Launch*& l, eden::Resolved& r) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
-    const std::vector<Launch>& L = encode ? pl->p.enc : pl->p.dec;
-    if (idx < 0 || idx >= (int)L.size()) return fail(OFL_EINVAL, "launch index out of range");
-    l = &L[idx];
-    if (const char* err = eden::resolve(pl->p, *l, encode != 0, pl->ncu, false, true, r)) return fail(OFL_EINVAL, err);
+static int resolve_plain(ofl_eden_plan_t pl, int encode, int idx, const Launch*& l, eden::Resolved& r, bool& rt) {
+    if (!pl || encode < 0 || encode > 2) return fail(OFL_EINVAL, "null plan or unknown launch list");
+    if (idx < 0 || idx >= num_launches(pl, encode)) return fail(OFL_EINVAL, "launch index out of range");
+    if (const char* err = resolve_at(pl, encode, idx, pl->ncu, false, true, l, r, rt)) return fail(OFL_EINVAL, err);
     return OFL_OK;
 }
 
@@ -3001,8 +3101,9 @@ int ofl_eden_plan_launch_info(ofl_eden_plan_t pl, int encode, int idx, char* nam
                               int64_t* bytes_moved, int64_t* bytes_alg) {
     const Launch* l = nullptr;
     eden::Resolved r;
-    if (int rc = resolve_plain(pl, encode, idx, l, r)) return rc;
-    if (name && cap > 0) snprintf(name, (size_t)cap, "%s", eden::kKernelName[r.id]);
+    bool rt = false;
+    if (int rc = resolve_plain(pl, encode, idx, l, r, rt)) return rc;
+    if (name && cap > 0) snprintf(name, (size_t)cap, "%s", rt ? eden::kRtKernelName[eden::RT_ROW] : eden::kKernelName[r.id]);
     if (blocks) *blocks = l->blocks;
     if (bytes_moved) *bytes_moved = l->bytes_moved;
     if (bytes_alg) *bytes_alg = l->bytes_alg;
@@ -3013,7 +3114,8 @@ int ofl_eden_plan_launch_detail(ofl_eden_plan_t pl, int encode, int idx, int32_t
                                 int64_t* grid) {
     const Launch* l = nullptr;
     eden::Resolved r;
-    if (int rc = resolve_plain(pl, encode, idx, l, r)) return rc;
+    bool rt = false;
+    if (int rc = resolve_plain(pl, encode, idx, l, r, rt)) return rc;
     if (explicit_tiles) *explicit_tiles = r.expl ? 1 : 0;
     if (paired) *paired = r.paired ? 1 : 0;
     if (grid) *grid = r.grid;
@@ -3021,10 +3123,10 @@ int ofl_eden_plan_launch_detail(ofl_eden_plan_t pl, int encode, int idx, int32_t
 }
 
 int ofl_eden_plan_profile_collect(ofl_eden_plan_t pl, int encode, double* ms_sum, int max, int* ncalls) {
-    if (!pl) return fail(OFL_EINVAL, "null plan");
+    if (!pl || encode < 0 || encode > 2) return fail(OFL_EINVAL, "null plan or unknown launch list");
     std::lock_guard<std::mutex> g(pl->mu);
-    auto& calls = pl->prof_ev[encode ? 1 : 0];
-    const int nl = (int)(encode ? pl->p.enc.size() : pl->p.dec.size());
+    auto& calls = pl->prof_ev[encode];
+    const int nl = num_launches(pl, encode);
     for (int i = 0; i < std::min(nl, max); ++i) ms_sum[i] = 0.0;
     for (auto& call : calls) {
         for (int i = 0; i < nl && i < max; ++i) {
