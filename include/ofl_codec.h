@@ -176,6 +176,29 @@ int ofl_eden_encode_wavg(ofl_eden_plan_t plan, const float* const* collab_arenas
 int ofl_eden_decode_add(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uint32_t* seeds,
                         const float* scales, const float* base_arena, float* y_arena, void* ws,
                         size_t ws_bytes, void* stream);
+/* decode fused with the streaming average (ofl_wavg_accumulate): one
+ * collaborator's planes straight into the float64 sums arena (the plan's
+ * layout, 8 bytes per element).  The plan's decode schedule runs as it is --
+ * the same waves, streams, fork / join and workspace
+ * (ofl_eden_plan_workspace_bytes) -- but the last row pass of the slices above
+ * 2^15 elements (k_dec_acc_rowC / k_dec_acc_rowC2 in place of k_dec_rowC /
+ * k_dec_rowC2) does not store y: per element i below the tensor's length,
+ *     x = base ? base[i] + decoded[i] : decoded[i]     (ofl_eden_decode_add's float32 bits)
+ *     sums[i] = first ? (double)x * w : sums[i] + (double)x * w
+ * i.e. ofl_wavg_accumulate's operations on ofl_eden_decode_add's y, the same
+ * bits (a first product of -0.0 is stored as -0.0), without y's 8 B/element
+ * round trip through HBM and without the arena-wide accumulate launch.
+ * Slices of at most 2^15 elements keep their decode kernels and write
+ * base + decoded into y_small (float32, the plan's layout, written on those
+ * slices' ranges only); the caller folds them, and whatever the codec does
+ * not touch, with ofl_wavg_accumulate_ranges.  Nothing of sums outside the
+ * large slices' valid elements is read or written.
+ * Null planes / seeds / scales / sums: OFL_EINVAL; null y_small: OFL_EINVAL
+ * when the plan has a slice of at most 2^15 elements; nothing is launched
+ * then.  Async and graph-capturable after the plan's first use, as decode. */
+int ofl_eden_decode_accumulate(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uint32_t* seeds,
+                               const float* scales, const float* base_arena /* nullable */, double w, int first,
+                               double* sums, float* y_small, void* ws, size_t ws_bytes, void* stream);
 /* The round trip y = decode(encode(x)) (+ base when given) with the bytes
  * discarded: what Aggregator._prepare_trained computes when nothing is sent
  * (aggregator.py:816-826), and the y of a collaborator's error feedback
@@ -273,7 +296,10 @@ int ofl_side_stream(int index, void** stream);
  * its grid size, the bytes it reads+writes in HBM and its share of the
  * algorithmic bytes (input/output fp32 + bit planes; FWHT intermediates 0).
  * `encode` names the launch list in all four calls below: 0 decode, 1 encode,
- * 2 the round trip (ofl_eden_roundtrip). */
+ * 2 the round trip (ofl_eden_roundtrip), 3 decode into the sums
+ * (ofl_eden_decode_accumulate: decode's launches, the last row passes under
+ * their own names and with the bytes of a delta upload after the first --
+ * intermediate 4, base 4, sums 8 + 8 per element, no algorithmic bytes). */
 int ofl_eden_plan_profile(ofl_eden_plan_t plan, int enable);
 int ofl_eden_plan_num_launches(ofl_eden_plan_t plan, int encode);
 int ofl_eden_plan_launch_info(ofl_eden_plan_t plan, int encode, int idx, char* name, int cap,
@@ -489,6 +515,12 @@ int ofl_apply_delta_ranges(const float* base, const float* delta, float* out, in
 int ofl_wavg_delta32_ranges(int ncollab, const float* const* xs, const double* weights, double wsum,
                             const float* base, int nranges, const int64_t* starts, const int64_t* dst, int64_t total,
                             float* delta32_out, void* stream);
+/* ofl_wavg_accumulate on listed ranges only (the same DEVICE tables; nothing
+ * synchronises): the elements ofl_eden_decode_accumulate leaves to the
+ * caller -- the slices of at most 2^15 elements and the tensors the codec
+ * does not touch.  sums and x are whole arenas; only the ranges are touched. */
+int ofl_wavg_accumulate_ranges(const float* x, double w, int first, int nranges, const int64_t* starts,
+                               const int64_t* dst, int64_t total, double* sums, void* stream);
 /* The robust aggregators a plan can name in aggregation_type, on the same
  * arenas.
  *

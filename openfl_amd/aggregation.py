@@ -704,15 +704,7 @@ class WavgAccumulator:
         if self.finished:
             raise _lib.CodecError("accumulator: add() after finish()")
         re._check_arena(arena)
-        try:
-            w = float(np.asarray(weight, np.float64).reshape(()))
-        except (TypeError, ValueError) as e:
-            raise _lib.CodecError(f"accumulator: weight {weight!r} is not a number") from e
-        if np.result_type(np.float32, np.asarray(weight).dtype) != np.float64:
-            _f64_weights(self.weights + [weight], len(self.weights) + 1)  # run()'s rule on the weights so far
-        c = len(self.weights)
-        if re.single and c >= _POINTS_MAX_C:
-            raise _lib.CodecError(f"accumulator: at most {_POINTS_MAX_C} collaborators with 1-element tensors")
+        w, c = self._next_weight(weight)
         with torch.cuda.device(re.device):
             _lib.check_agg(_lib.lib().ofl_wavg_accumulate(arena.data_ptr(), w, 1 if c == 0 else 0, re.arena_numel,
                                                           self.sums.data_ptr(), _stream(re.device)))
@@ -720,13 +712,57 @@ class WavgAccumulator:
                 torch.index_select(arena, 0, re._single_idx, out=self._row(c))
         self.weights.append(weight)
 
-    def add_upload(self, items, weight, lossless=False, delta=True, base_arena=None):
-        """re.ingest(items, ...) into this accumulator's own scratch arena,
-        then add(that, weight): one collaborator's upload as it arrives."""
+    def _next_weight(self, weight):
+        """add()'s checks of the next collaborator's weight -> (its float64
+        value, the collaborator's index)."""
+        try:
+            w = float(np.asarray(weight, np.float64).reshape(()))
+        except (TypeError, ValueError) as e:
+            raise _lib.CodecError(f"accumulator: weight {weight!r} is not a number") from e
+        if np.result_type(np.float32, np.asarray(weight).dtype) != np.float64:
+            _f64_weights(self.weights + [weight], len(self.weights) + 1)  # run()'s rule on the weights so far
+        c = len(self.weights)
+        if self.re.single and c >= _POINTS_MAX_C:
+            raise _lib.CodecError(f"accumulator: at most {_POINTS_MAX_C} collaborators with 1-element tensors")
+        return w, c
+
+    def add_upload(self, items, weight, lossless=False, delta=True, base_arena=None, fused=None):
+        """One collaborator's upload as it arrives.  fused=False:
+        re.ingest(items, ...) into this accumulator's own scratch arena, then
+        add(that, weight).  fused=True: an Eden-coded upload (lossless=False,
+        a layout with tensors above dim_threshold) is decoded straight into
+        the sums -- ofl_eden_decode_accumulate: the slices above 2^15 elements
+        never cross HBM as float32, and there is no arena-wide accumulate
+        launch; the raw tensors and the slices of at most 2^15 elements go
+        through the scratch and one ofl_wavg_accumulate_ranges.  The sums'
+        bits on every tensor are the unfused path's.  CodecError where that
+        does not apply.  fused=None (default): fused where it applies.  Every
+        check of ingest() and add() raises before anything is launched."""
         if self.finished:
             raise _lib.CodecError("accumulator: add_upload() after finish()")
-        self._scratch = self.re.ingest(items, lossless=lossless, delta=delta, base_arena=base_arena, out=self._scratch)
-        self.add(self._scratch, weight)
+        re = self.re
+        dev = resolve_device(getattr(re, "device", None))
+        applies = re._lossy is None and not lossless and re.plan is not None
+        if fused and not applies:
+            raise _lib.CodecError("add_upload(fused=True) takes an Eden pipeline's lossy_compressed upload into a "
+                                  "layout with tensors above dim_threshold")
+        if not applies or (fused is not None and not fused):
+            self._scratch = re.ingest(items, lossless=lossless, delta=delta, base_arena=base_arena, out=self._scratch)
+            return self.add(self._scratch, weight)
+        items, bufs = re._ingest_begin(items, "eden", delta, base_arena, self._scratch)
+        w, c = self._next_weight(weight)
+        with torch.cuda.device(dev):
+            if self._scratch is None:
+                self._scratch = re._empty_arena()
+            # the scratch: ingest's arena on the _fz ranges only (raw tensors, small slices)
+            re._ingest_eden(items, bufs, base_arena if delta else None, self._scratch, fold=(self.sums, w, c == 0))
+            _lib.check_agg(_lib.lib().ofl_wavg_accumulate_ranges(self._scratch.data_ptr(), w, 1 if c == 0 else 0,
+                                                                  *re._fz.args, self.sums.data_ptr(), _stream(dev)))
+            if re.single:
+                torch.index_select(self._scratch, 0, re._single_idx, out=self._row(c))
+            if c == 0 and re._gap_idx is not None:
+                self.sums.index_fill_(0, re._gap_idx, 0.0)
+        self.weights.append(weight)
 
 
 class AdaptiveAccumulator:
@@ -949,6 +985,18 @@ class RoundEnd:
         Not thread-safe per RoundEnd: it uses the instance's staging and
         decode arena, and the current stream."""
         dev = resolve_device(getattr(self, "device", None))
+        kind = "raw" if lossless else "eden" if self._lossy is None else "lossy"
+        items, bufs = self._ingest_begin(items, kind, delta, base_arena, out)
+        with torch.cuda.device(dev):
+            if out is None:
+                out = self._empty_arena()
+            getattr(self, "_ingest_" + kind)(items, bufs, base_arena if delta else None, out)
+            self._zero_gaps(out)
+        return out
+
+    def _ingest_begin(self, items, kind, delta, base_arena, out):
+        """Every check ingest makes before it writes or launches anything ->
+        (the items as a list, _ingest_check's payload arrays)."""
         items = list(items)
         T = len(self.numels)
         if len(items) != T:
@@ -958,14 +1006,7 @@ class RoundEnd:
         for a in (base_arena, out):
             if a is not None:
                 self._check_arena(a)
-        kind = "raw" if lossless else "eden" if self._lossy is None else "lossy"
-        bufs = self._ingest_check(items, kind)
-        with torch.cuda.device(dev):
-            if out is None:
-                out = self._empty_arena()
-            getattr(self, "_ingest_" + kind)(items, bufs, base_arena if delta else None, out)
-            self._zero_gaps(out)
-        return out
+        return items, self._ingest_check(items, kind)
 
     def _ingest_check(self, items, kind):
         """ingest's checks of the items, all before anything is written ->
@@ -1076,9 +1117,12 @@ class RoundEnd:
             _lib.check_agg(_lib.lib().ofl_apply_delta(base.data_ptr(), dst.data_ptr(), self.arena_numel, out.data_ptr(),
                                                       _stream(self.device)))
 
-    def _ingest_eden(self, items, bufs, base, out):
+    def _ingest_eden(self, items, bufs, base, out, fold=None):
         """EdenPipeline's payloads: the big tensors' planes, scales and seeds in
-        one H2D and one batch decode (which adds the base); the rest are raw."""
+        one H2D and one batch decode (which adds the base); the rest are raw.
+        fold = (sums, weight, first), WavgAccumulator.add_upload's fused path:
+        the batch decode folds the slices above 2^15 elements into sums
+        (EdenPlan.decode_accumulate) and writes only the smaller ones to out."""
         dev, p = self.device, self.plan
         raw = [i for i, n in enumerate(self.numels) if 0 < n <= self.dim_threshold]
         off_scales = (p.planes_bytes + 255) // 256 * 256 if p is not None else 0
@@ -1105,9 +1149,17 @@ class RoundEnd:
             d.copy_(host, non_blocking=True)
             if self._codec_ws is None or self._codec_ws.numel() < p.ws_bytes:
                 self._codec_ws = torch.empty(max(p.ws_bytes, 256), dtype=torch.uint8, device=dev)
-            p.decode(d[:max(p.planes_bytes, 1)], d[off_seeds:].view(torch.int32),
-                     d[off_scales:off_scales + 4 * p.n_slices].view(torch.float32), out, self._codec_ws, base=base)
-        self._ingest_sent()
+            planes, seeds_d = d[:max(p.planes_bytes, 1)], d[off_seeds:].view(torch.int32)
+            scales_d = d[off_scales:off_scales + 4 * p.n_slices].view(torch.float32)
+            if fold is None:
+                p.decode(planes, seeds_d, scales_d, out, self._codec_ws, base=base)
+            else:
+                # the staging is free once its copies have run: the next upload's
+                # staging does not wait for this one's decode and fold as well
+                self._ingest_sent()
+                p.decode_accumulate(planes, seeds_d, scales_d, *fold, out, self._codec_ws, base=base)
+        if fold is None:
+            self._ingest_sent()
         if raw and base is not None:
             _lib.check_agg(_lib.lib().ofl_apply_delta_ranges(base.data_ptr(), dst.data_ptr(), out.data_ptr(),
                                                              *self._rest.args, _stream(dev)))

@@ -452,6 +452,18 @@ __global__ __launch_bounds__(kNT) void k_wavg_delta32_ranges(WavgArgs a, Ranges 
     }
 }
 
+// k_wavg_accumulate (acc_elem) on listed ranges only: the elements a fused
+// decode-accumulate does not fold itself (ofl_eden_decode_accumulate: slices
+// of <= 2^15 elements and the tensors the codec does not touch)
+__global__ __launch_bounds__(kNT) void k_wavg_accumulate_ranges(AccArgs a, Ranges rg) {
+    const int64_t total = rg.total();
+    for (int64_t j = (int64_t)blockIdx.x * kNT + threadIdx.x; j < total; j += (int64_t)gridDim.x * kNT) {
+        int64_t i;
+        rg.find(j, i);
+        acc_elem(a, i);
+    }
+}
+
 __global__ __launch_bounds__(64) void k_py_hash(const double* v, int n, int64_t* out) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i < n) out[i] = py_hash_double(v[i]);
@@ -670,6 +682,17 @@ int ofl_wavg_delta32_ranges(int ncollab, const float* const* xs, const double* w
     a.last = 1;
     a.o = {base, nullptr, nullptr, delta32_out};
     hipLaunchKernelGGL(agg::k_wavg_delta32_ranges, dim3(grid_for(total, 1)), dim3(agg::kNT), 0,
+                       static_cast<hipStream_t>(stream), a, agg::Ranges{starts, dst, nranges});
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_wavg_accumulate_ranges(const float* x, double w, int first, int nranges, const int64_t* starts,
+                               const int64_t* dst, int64_t total, double* sums, void* stream) {
+    if (nranges < 1 || total <= 0) return OFL_OK;
+    if (!x || !sums || !starts || !dst) return afail(OFL_EINVAL, "wavg_accumulate_ranges: bad arguments");
+    agg::AccArgs a{x, w, first ? 1 : 0, sums, total};
+    hipLaunchKernelGGL(agg::k_wavg_accumulate_ranges, dim3(grid_for(total, 1)), dim3(agg::kNT), 0,
                        static_cast<hipStream_t>(stream), a, agg::Ranges{starts, dst, nranges});
     AHIP(hipGetLastError());
     return OFL_OK;

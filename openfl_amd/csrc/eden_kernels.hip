@@ -55,6 +55,7 @@
 #include "eden_desc.h"
 #include "eden_plan.h"
 #include "eden_rt_plan.h"
+#include "eden_acc_plan.h"
 #include "eden_tables.h"
 #include "lds_exchange.h"
 #include "ofl_codec.h"
@@ -103,7 +104,14 @@ struct KArgs {
     float* xout;            // fp32 arena out (decode)
     float* ws;              // intermediate buffer base
     const uint8_t* pin;     // planes in (decode)
-    uint8_t* pout;          // planes out (encode)
+    // decode into the streaming average (ofl_eden_decode_accumulate,
+    // eden_dec_acc.h) shares three encode-only places, so the argument block
+    // keeps its size: the large slices' last row pass folds (base +) decoded
+    // times acc_w into the float64 sums instead of storing y
+    union {
+        uint8_t* pout;      // planes out (encode)
+        double* sums;       // the sums arena (decode-accumulate)
+    };
     const uint32_t* seeds;
     float* scales;          // encode: out
     const float* scales_in; // decode: in
@@ -117,8 +125,12 @@ struct KArgs {
     const float* const* wx; // collaborator arenas (device array of wc pointers), nullable
     const double* ww;       // their weights (device)
     const float* wbase;     // base model arena, nullable
-    double wsum;            // NumPy's float64 sum of the weights
+    union {
+        double wsum;        // NumPy's float64 sum of the weights
+        double acc_w;       // the collaborator's weight (decode-accumulate)
+    };
     int32_t wc;             // collaborators (1..16)
+    int32_t acc_first;      // decode-accumulate: store the product instead of adding it
     // fused column + small-set launches (k_enc_colm_set / k_dec_colm_set):
     // blocks < sset_first run the small-set groups of table sset
     const int32_t* sset;
@@ -130,6 +142,7 @@ struct KArgs {
     // but in those two) for a split 5-pass slice's sub-waves
     int32_t npair;
 };
+static_assert(sizeof(KArgs) == 192, "KArgs: the kernels' argument block keeps its size (the hidden arguments follow it)");
 
 // Eden centroids in global memory (copied to LDS per workgroup); the
 // bucketize boundaries live in the quantiser table below
@@ -2307,6 +2320,8 @@ __global__ __launch_bounds__(256) void k_finalize(KArgs a) {
 
 // the round trip's row pass (k_rt_row), after every kernel above
 #include "eden_rt_row.h"
+// decode's last row pass into the streaming average's sums, after it
+#include "eden_dec_acc.h"
 
 }  // namespace ofl
 
@@ -2333,7 +2348,7 @@ struct ofl_eden_plan {
     const char* rt_err = nullptr;  // why the plan has none (ofl_eden_roundtrip reports it)
     // profiling: events around every launch of every call while enabled
     bool prof = false;
-    std::vector<std::vector<hipEvent_t>> prof_ev[3];  // [dec, enc, round trip][call][launch+1]
+    std::vector<std::vector<hipEvent_t>> prof_ev[4];  // [dec, enc, round trip, decode-accumulate][call][launch+1]
     std::vector<hipEvent_t> ev_pool;
     ofl::SliceDesc* d_slices = nullptr;
     ofl::SliceDesc* d_rt_slices = nullptr;  // rt.slices
@@ -2419,9 +2434,18 @@ constexpr KernelEntry kRtKernels[eden::RT_KERNEL_COUNT] = {
     {eden::KERNEL_COUNT, ofl::k_rt_row, ofl::kRowNT, ofl::kRowC2Smem},
 };
 
+// decode-accumulate's own kernels, one entry per eden::AccKernelId (the LDS of the kernels they stand in for)
+constexpr KernelEntry kAccKernels[eden::ACC_KERNEL_COUNT] = {
+    {eden::KERNEL_COUNT, ofl::k_dec_acc_rowC, ofl::kRowNT, ofl::kRowSmemA},
+    {eden::KERNEL_COUNT, ofl::k_dec_acc_rowC2, ofl::kRowNT, ofl::kRow2Smem},
+};
+
 hipError_t set_all_attrs() {
-    for (const KernelEntry* tab : {kKernels, kRtKernels})
-        for (int i = 0; i < (tab == kKernels ? (int)eden::KERNEL_COUNT : (int)eden::RT_KERNEL_COUNT); ++i) {
+    const std::pair<const KernelEntry*, int> tabs[] = {{kKernels, (int)eden::KERNEL_COUNT},
+                                                       {kRtKernels, (int)eden::RT_KERNEL_COUNT},
+                                                       {kAccKernels, (int)eden::ACC_KERNEL_COUNT}};
+    for (const auto& [tab, n] : tabs)
+        for (int i = 0; i < n; ++i) {
             const KernelEntry& k = tab[i];
             if (k.lds == 0) continue;
             const hipError_t e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
@@ -2431,25 +2455,41 @@ hipError_t set_all_attrs() {
 }
 
 // which of a plan's launch lists a call runs (the ABI's `encode` argument)
-enum { RUN_DEC = 0, RUN_ENC = 1, RUN_RT = 2 };
+enum { RUN_DEC = 0, RUN_ENC = 1, RUN_RT = 2, RUN_ACC = 3, RUN_COUNT };
 int num_launches(const ofl_eden_plan* pl, int which) {
     return (int)(which == RUN_RT ? pl->rt.list.size() : which == RUN_ENC ? pl->p.enc.size() : pl->p.dec.size());
 }
 // launch idx of a list and what it runs (ncu CUs; wavg: the weighted-average
-// first pass; planes8: eden::resolve).  rt: k_rt_row, else kKernels[r.id]
-const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, bool wavg, bool planes8, const Launch*& l,
-                       eden::Resolved& r, bool& rt) {
-    rt = false;
+// first pass; planes8: eden::resolve): kKernels[r.id], or the round trip's or
+// decode-accumulate's own kernel in its place
+struct Picked {
+    const Launch* l;
+    eden::Resolved r;
+    const KernelEntry* k;
+    const char* name;
+    bool acc;  // a decode-accumulate row launch (its bytes: eden::acc_bytes_moved)
+};
+const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, bool wavg, bool planes8, Picked& p) {
+    const char* err = nullptr;
+    int rt = -1, acc = -1;
     if (which == RUN_RT) {
         eden::RtResolved x;
-        l = &pl->rt.list[idx].l;
-        const char* err = eden::rt_resolve(pl->p, pl->rt.list[idx], ncu, wavg, x);
-        r = x.r;
-        rt = x.rt;
-        return err;
+        p.l = &pl->rt.list[idx].l;
+        err = eden::rt_resolve(pl->p, pl->rt.list[idx], ncu, wavg, x);
+        p.r = x.r;
+        if (x.rt) rt = eden::RT_ROW;
+    } else if (which == RUN_ACC) {
+        p.l = &pl->p.dec[idx];
+        err = eden::acc_resolve(pl->p, *p.l, ncu, planes8, p.r, acc);
+    } else {
+        p.l = &(which == RUN_ENC ? pl->p.enc : pl->p.dec)[idx];
+        err = eden::resolve(pl->p, *p.l, which == RUN_ENC, ncu, wavg, planes8, p.r);
     }
-    l = &(which == RUN_ENC ? pl->p.enc : pl->p.dec)[idx];
-    return eden::resolve(pl->p, *l, which == RUN_ENC, ncu, wavg, planes8, r);
+    if (err) return err;
+    p.acc = acc >= 0;
+    p.k = rt >= 0 ? &kRtKernels[rt] : acc >= 0 ? &kAccKernels[acc] : &kKernels[p.r.id];
+    p.name = rt >= 0 ? eden::kRtKernelName[rt] : acc >= 0 ? eden::kAccKernelName[acc] : eden::kKernelName[p.r.id];
+    return nullptr;
 }
 
 int run(ofl_eden_plan* pl, int which, const ofl::KArgs& base, hipStream_t caller) {
@@ -2482,12 +2522,11 @@ int run(ofl_eden_plan* pl, int which, const ofl::KArgs& base, hipStream_t caller
     const bool wavg = base.wx != nullptr;
     const bool planes8 = (reinterpret_cast<uintptr_t>(base.pin) & 7u) == 0;
     for (size_t li = 0; li < nl; ++li) {
-        const Launch* lp = nullptr;
-        eden::Resolved r;
-        bool rt = false;
-        if (const char* err = resolve_at(pl, which, (int)li, pl->ncu, wavg, planes8, lp, r, rt)) return fail(OFL_EINVAL, err);
-        const Launch& l = *lp;
-        const KernelEntry& k = rt ? kRtKernels[eden::RT_ROW] : kKernels[r.id];
+        Picked pk;
+        if (const char* err = resolve_at(pl, which, (int)li, pl->ncu, wavg, planes8, pk)) return fail(OFL_EINVAL, err);
+        const Launch& l = *pk.l;
+        const eden::Resolved& r = pk.r;
+        const KernelEntry& k = *pk.k;
         const hipStream_t st = streams[l.stream];
         ofl::KArgs a = base;
         a.list = pl->d_ints + l.list_off;
@@ -2809,6 +2848,27 @@ int ofl_eden_decode_add(ofl_eden_plan_t pl, const uint8_t* planes_arena, const u
     return run(pl, RUN_DEC, a, static_cast<hipStream_t>(stream));
 }
 
+int ofl_eden_decode_accumulate(ofl_eden_plan_t pl, const uint8_t* planes_arena, const uint32_t* seeds,
+                               const float* scales, const float* base_arena, double w, int first, double* sums,
+                               float* y_small, void* ws, size_t ws_bytes, void* stream) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    if (!planes_arena || !seeds || !scales || !sums) return fail(OFL_EINVAL, "decode_accumulate: null argument");
+    if (!y_small && eden::has_small_slice(pl->p))
+        return fail(OFL_EINVAL, "decode_accumulate: the plan has slices of at most 2^15 elements, which need y_small");
+    ofl::KArgs a;
+    int rc = prep_args(pl, a, ws, ws_bytes);
+    if (rc) return rc;
+    a.pin = planes_arena;
+    a.xout = y_small;  // the tiny / small slices' decode kernels alone write it
+    a.yadd = base_arena;
+    a.seeds = seeds;
+    a.scales_in = scales;
+    a.sums = sums;
+    a.acc_w = w;
+    a.acc_first = first ? 1 : 0;
+    return run(pl, RUN_ACC, a, static_cast<hipStream_t>(stream));
+}
+
 int64_t ofl_eden_roundtrip_workspace_bytes(ofl_eden_plan_t pl) {
     return pl && !pl->rt_err ? eden::rt_workspace_bytes(pl->p, pl->rt) : -1;
 }
@@ -3075,7 +3135,7 @@ int ofl_copy_h2d_staged(void* dst_dev, const void* src_host, size_t bytes, int n
 int ofl_eden_plan_profile(ofl_eden_plan_t pl, int enable) {
     if (!pl) return fail(OFL_EINVAL, "null plan");
     std::lock_guard<std::mutex> g(pl->mu);
-    for (int d = 0; d < 3; ++d) {
+    for (int d = 0; d < RUN_COUNT; ++d) {
         for (auto& call : pl->prof_ev[d]) pl->ev_pool.insert(pl->ev_pool.end(), call.begin(), call.end());
         pl->prof_ev[d].clear();
     }
@@ -3084,46 +3144,42 @@ int ofl_eden_plan_profile(ofl_eden_plan_t pl, int enable) {
 }
 
 int ofl_eden_plan_num_launches(ofl_eden_plan_t pl, int encode) {
-    if (!pl || encode < 0 || encode > 2) return fail(OFL_EINVAL, "null plan or unknown launch list");
+    if (!pl || encode < 0 || encode >= RUN_COUNT) return fail(OFL_EINVAL, "null plan or unknown launch list");
     return num_launches(pl, encode);
 }
 
 // What a launch of a plain encode / decode (no weighted average, aligned
 // planes) resolves to on the plan's device (256 CUs before its first use)
-static int resolve_plain(ofl_eden_plan_t pl, int encode, int idx, const Launch*& l, eden::Resolved& r, bool& rt) {
-    if (!pl || encode < 0 || encode > 2) return fail(OFL_EINVAL, "null plan or unknown launch list");
+static int resolve_plain(ofl_eden_plan_t pl, int encode, int idx, Picked& p) {
+    if (!pl || encode < 0 || encode >= RUN_COUNT) return fail(OFL_EINVAL, "null plan or unknown launch list");
     if (idx < 0 || idx >= num_launches(pl, encode)) return fail(OFL_EINVAL, "launch index out of range");
-    if (const char* err = resolve_at(pl, encode, idx, pl->ncu, false, true, l, r, rt)) return fail(OFL_EINVAL, err);
+    if (const char* err = resolve_at(pl, encode, idx, pl->ncu, false, true, p)) return fail(OFL_EINVAL, err);
     return OFL_OK;
 }
 
 int ofl_eden_plan_launch_info(ofl_eden_plan_t pl, int encode, int idx, char* name, int cap, int64_t* blocks,
                               int64_t* bytes_moved, int64_t* bytes_alg) {
-    const Launch* l = nullptr;
-    eden::Resolved r;
-    bool rt = false;
-    if (int rc = resolve_plain(pl, encode, idx, l, r, rt)) return rc;
-    if (name && cap > 0) snprintf(name, (size_t)cap, "%s", rt ? eden::kRtKernelName[eden::RT_ROW] : eden::kKernelName[r.id]);
-    if (blocks) *blocks = l->blocks;
-    if (bytes_moved) *bytes_moved = l->bytes_moved;
-    if (bytes_alg) *bytes_alg = l->bytes_alg;
+    Picked p;
+    if (int rc = resolve_plain(pl, encode, idx, p)) return rc;
+    if (name && cap > 0) snprintf(name, (size_t)cap, "%s", p.name);
+    if (blocks) *blocks = p.l->blocks;
+    if (bytes_moved) *bytes_moved = p.acc ? eden::acc_bytes_moved(*p.l) : p.l->bytes_moved;
+    if (bytes_alg) *bytes_alg = p.acc ? 0 : p.l->bytes_alg;
     return OFL_OK;
 }
 
 int ofl_eden_plan_launch_detail(ofl_eden_plan_t pl, int encode, int idx, int32_t* explicit_tiles, int32_t* paired,
                                 int64_t* grid) {
-    const Launch* l = nullptr;
-    eden::Resolved r;
-    bool rt = false;
-    if (int rc = resolve_plain(pl, encode, idx, l, r, rt)) return rc;
-    if (explicit_tiles) *explicit_tiles = r.expl ? 1 : 0;
-    if (paired) *paired = r.paired ? 1 : 0;
-    if (grid) *grid = r.grid;
+    Picked p;
+    if (int rc = resolve_plain(pl, encode, idx, p)) return rc;
+    if (explicit_tiles) *explicit_tiles = p.r.expl ? 1 : 0;
+    if (paired) *paired = p.r.paired ? 1 : 0;
+    if (grid) *grid = p.r.grid;
     return OFL_OK;
 }
 
 int ofl_eden_plan_profile_collect(ofl_eden_plan_t pl, int encode, double* ms_sum, int max, int* ncalls) {
-    if (!pl || encode < 0 || encode > 2) return fail(OFL_EINVAL, "null plan or unknown launch list");
+    if (!pl || encode < 0 || encode >= RUN_COUNT) return fail(OFL_EINVAL, "null plan or unknown launch list");
     std::lock_guard<std::mutex> g(pl->mu);
     auto& calls = pl->prof_ev[encode];
     const int nl = num_launches(pl, encode);

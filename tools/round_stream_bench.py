@@ -23,6 +23,9 @@ One process, windows alternated (A B A B A B, the minimum and the spread of each
               read again and the float32 gradient read and written per add), and ofl_adaptive_accumulate
               and ofl_adaptive_finish alone beside ofl_wavg_accumulate,
               ofl_wavg_finish and k_adaptive in bytes per second (adaptive_stream).
+  --upload-stream   instead: the round end from Eden-coded uploads, add_upload x
+              C + finish, the decode fused with the accumulate against ingest +
+              add, and the last row passes alone (upload_stream).
 Prints one JSON line.
 """
 import argparse
@@ -231,6 +234,120 @@ def adaptive_stream(args):
                  "kernels": kernels}}), flush=True)
 
 
+def upload_stream(args):
+    """--upload-stream: the round end fed with Eden-coded uploads, add_upload x
+    C + finish, with the decode folded into the sums (fused=True:
+    ofl_eden_decode_accumulate) against ingest + add (fused=False), alternated
+    windows in one process; then, under the plan's launch events, the last
+    row passes alone: k_dec_acc_rowC / k_dec_acc_rowC2 (ws 4 + base 4 + sums
+    8 + 8 B per element; the first upload reads no sums) beside k_dec_rowC /
+    k_dec_rowC2 (ws 4 + base 4 + y 4) plus ofl_wavg_accumulate (y 4 + sums
+    8 + 8), both by bytes over time.  On a commit whose add_upload has no
+    fused= the unfused windows run alone, for the parent's figure."""
+    import inspect
+    import torch
+    from openfl_amd import _lib
+    from openfl_amd import aggregation as A
+    from openfl_amd.pipelines import EdenPipeline
+    from openfl_amd.workloads import WORKLOADS
+    dev = torch.device("cuda", 0)
+    shapes = [tuple(s) for _, s in WORKLOADS[args.workload]()]
+    pipe = EdenPipeline(n_bits=8, device=dev, seed_mode="fast")
+    re = A.RoundEnd(pipe, shapes, dev)
+    C, n = args.collaborators, re.arena_numel
+    g = torch.Generator(device=dev)
+    arenas = []
+    for c in range(C + 1):
+        g.manual_seed(1000 + c)
+        a = torch.empty(n, dtype=torch.float32, device=dev).normal_(0.0, 0.01, generator=g)
+        re._zero_gaps(a)
+        arenas.append(a)
+    base = arenas[0]
+    uploads = [pipe.forward_batch([re.view(a, i).cpu().numpy() for i in range(len(shapes))]) for a in arenas[1:]]
+    w = [float(v) for v in np.random.default_rng(0).random(C) + 0.5]
+    out = torch.empty_like(base)
+    sums = torch.empty(n, dtype=torch.float64, device=dev)
+    has_fused = "fused" in inspect.signature(A.WavgAccumulator.add_upload).parameters
+    np.random.seed(0)
+
+    def round_end(**kw):
+        acc = re.accumulator(sums=sums)
+        for items, wc in zip(uploads, w):
+            acc.add_upload(items, wc, delta=True, base_arena=base, **kw)
+        re.finish(acc, base_arena=base, payloads=False, out=out)
+        return acc
+
+    def timed(fn, steps):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / steps
+
+    fns = {"unfused": lambda: round_end(fused=False), "fused": lambda: round_end(fused=True)} if has_fused \
+        else {"unfused_parent": round_end}
+    times = {k: [] for k in fns}
+    for _ in range(WINDOWS):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, args.steps))
+    result = {"ms_per_round": {k: {"min": round(min(ts), 4), "max": round(max(ts), 4), "windows": [round(t, 4) for t in ts]}
+                               for k, ts in times.items()}}
+    if has_fused:
+        results = {}
+        for k, fn in fns.items():
+            np.random.seed(0)   # finish() draws the seeds' offsets
+            fn()
+            torch.cuda.synchronize()
+            results[k] = (sums.clone(), out.clone())
+        result["same_bits"] = all(torch.equal(results["fused"][j][o:o + m], results["unfused"][j][o:o + m])
+                                  for j in (0, 1) for o, m in zip(re.offsets, re.numels))
+        # the last row passes alone: launch events of the plan over `reps` rounds
+        p, reps = re.plan, max(args.steps, 10)
+        big = sum(ln for t, i in enumerate(re.big) for P, ln in zip(p.dims[t], A.slice_plan(re.numels[i])[1]) if P > 1 << 15)
+        rows = {}
+        for k, which, rowk in (("unfused", 0, ("ofl::k_dec_rowC", "ofl::k_dec_rowC2")),
+                               ("fused", 3, ("ofl::k_dec_acc_rowC", "ofl::k_dec_acc_rowC2"))):
+            names = [l["name"] for l in p._launches(which)]
+            p.profile(True)
+            for _ in range(reps):
+                fns[k]()
+            torch.cuda.synchronize()
+            ms, calls = p.profile_collect(which)
+            p.profile(False)
+            rows[k] = {"kernels": sorted({nm for nm in names if nm in rowk}), "calls": calls,
+                       "ms_per_upload": round(sum(m for m, nm in zip(ms, names) if nm in rowk) / calls, 5)}
+        st = torch.cuda.current_stream(dev).cuda_stream
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        acc_ms = []
+        for _ in range(reps):
+            ev[0].record()
+            _lib.check_agg(_lib.lib().ofl_wavg_accumulate(base.data_ptr(), 1.0, 0, n, sums.data_ptr(), st))
+            ev[1].record()
+            torch.cuda.synchronize()
+            acc_ms.append(ev[0].elapsed_time(ev[1]))
+        t_acc = min(acc_ms)
+        t_un, t_fu = rows["unfused"]["ms_per_upload"], rows["fused"]["ms_per_upload"]
+        # per upload, averaged over a round of C: one first upload in C
+        b_un_row, b_fu = 12 * big, (24 * (C - 1) + 16) * big / C
+        result["row_kernels"] = {
+            "large_slice_elements": big, "arena_elements": n,
+            "unfused": dict(rows["unfused"], bytes_per_element=12, TBps=round(b_un_row / t_un / 1e9, 3)),
+            "wavg_accumulate_whole_arena": {"ms": round(t_acc, 5), "bytes_per_element": 20,
+                                            "TBps": round(20 * n / t_acc / 1e9, 3)},
+            "unfused_row_plus_accumulate": {"ms": round(t_un + t_acc, 5), "bytes_per_element": 32,
+                                            "TBps": round((b_un_row + 20 * n) / (t_un + t_acc) / 1e9, 3)},
+            "fused": dict(rows["fused"], bytes_per_element="24 (16 on the first upload of the round)",
+                          TBps=round(b_fu / t_fu / 1e9, 3))}
+    print(json.dumps({"metric": "ms, round end from Eden-coded uploads: add_upload x C + finish, decode fused with the "
+                                "streaming accumulate against ingest + add",
+                      "workload": args.workload, "collaborators": C, "windows": WINDOWS, "steps_per_window": args.steps,
+                      "warmup": args.warmup, "wire_bytes_per_upload": sum(len(b) for b, _ in uploads[0]), **result}),
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="resnet50_fp32")
@@ -240,9 +357,13 @@ def main():
     ap.add_argument("--ingest-steps", type=int, default=3)
     ap.add_argument("--lossy-ingest", action="store_true", help="only the KC / SKC / STC ingest A/B")
     ap.add_argument("--aggregation", choices=("adam", "yogi", "adagrad"), help="only the streamed FedOpt round end A/B")
+    ap.add_argument("--upload-stream", action="store_true",
+                    help="only the upload-streamed round end A/B: add_upload(fused=False | True) x C + finish")
     args = ap.parse_args()
     if args.lossy_ingest:
         return lossy_ingest(args)
+    if args.upload_stream:
+        return upload_stream(args)
     if args.aggregation:
         return adaptive_stream(args)
 
