@@ -199,6 +199,43 @@ int ofl_eden_decode_add(ofl_eden_plan_t plan, const uint8_t* planes_arena, const
 int ofl_eden_decode_accumulate(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uint32_t* seeds,
                                const float* scales, const float* base_arena /* nullable */, double w, int first,
                                double* sums, float* y_small, void* ws, size_t ws_bytes, void* stream);
+/* encode from and decode into bfloat16 arenas (bf16 passed as uint16_t; the
+ * plan's layout in elements, 2 bytes each).  The plan's schedules run as they
+ * are -- the same waves, streams, fork / join and workspace
+ * (ofl_eden_plan_workspace_bytes) -- but on the slices above 2^15 elements
+ * encode's first row pass reads x as bf16 (k_enc_rowA_bf16 / k_enc_rowA2_bf16
+ * in place of k_enc_rowA / k_enc_rowA2) and decode's last row pass writes y as
+ * bf16 (k_dec_rowC_bf16 / k_dec_rowC2_bf16 in place of k_dec_rowC /
+ * k_dec_rowC2).  Widening bf16 is exact, so planes and scales are, byte for
+ * byte, ofl_eden_encode's on the widened arena; per element i below the
+ * tensor's length
+ *     y[i] = bf16(base ? float32(widen(base[i]) + decoded[i]) : decoded[i])
+ * i.e. ofl_eden_decode_add's float32 y on the widened base, rounded to
+ * nearest even (the largest finite values to inf; a NaN stays a NaN with its
+ * sign).  Nothing of y outside the tensors' elements is written.
+ * Slices of at most 2^15 elements keep their kernels on a float32 side arena
+ * of ofl_eden_bf16_side_numel() elements, 16-byte aligned, that holds those
+ * slices' elements alone (packed range by range; the layout is the
+ * library's): its size follows the small slices, not the arena -- at most 3
+ * elements of padding per run of neighbouring small slices, 0 for a plan
+ * without such a slice.  x_small is filled from x_arena before the encode,
+ * y_small is written by the decode and rounded (+ base) into y_arena after
+ * it, by one range launch each on `stream`; one buffer may serve both and
+ * every call of the plan, but is scratch of the call like ws: calls that may
+ * run at the same time (other streams) need side arenas of their own.  NULL
+ * is allowed when the size is 0.  y_arena may alias base_arena.
+ * The bf16 arenas must be 8-byte aligned and the plan's tensor offsets
+ * multiples of 4 elements (the default layout's are multiples of 64): the row
+ * passes move 4 elements per access.
+ * Null x / seeds / planes / scales / y, a missing side arena or a misaligned
+ * arena: OFL_EINVAL, nothing launched.  Async on `stream` and
+ * graph-capturable after the plan's first such call, as encode / decode. */
+int64_t ofl_eden_bf16_side_numel(ofl_eden_plan_t plan);   /* -1: null plan; host only */
+int ofl_eden_encode_bf16(ofl_eden_plan_t plan, const uint16_t* x_arena, float* x_small, const uint32_t* seeds,
+                         uint8_t* planes_arena, float* scales, void* ws, size_t ws_bytes, void* stream);
+int ofl_eden_decode_add_bf16(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uint32_t* seeds,
+                             const float* scales, const uint16_t* base_arena /* nullable */, uint16_t* y_arena,
+                             float* y_small, void* ws, size_t ws_bytes, void* stream);
 /* The round trip y = decode(encode(x)) (+ base when given) with the bytes
  * discarded: what Aggregator._prepare_trained computes when nothing is sent
  * (aggregator.py:816-826), and the y of a collaborator's error feedback
@@ -299,7 +336,11 @@ int ofl_side_stream(int index, void** stream);
  * 2 the round trip (ofl_eden_roundtrip), 3 decode into the sums
  * (ofl_eden_decode_accumulate: decode's launches, the last row passes under
  * their own names and with the bytes of a delta upload after the first --
- * intermediate 4, base 4, sums 8 + 8 per element, no algorithmic bytes). */
+ * intermediate 4, base 4, sums 8 + 8 per element, no algorithmic bytes),
+ * 4 encode from and 5 decode into bf16 arenas (ofl_eden_encode_bf16 /
+ * ofl_eden_decode_add_bf16: the plan's launches, the first / last row passes
+ * under their own names with 2 arena bytes per element instead of 4; the two
+ * range launches of the small slices' side arena are not listed). */
 int ofl_eden_plan_profile(ofl_eden_plan_t plan, int enable);
 int ofl_eden_plan_num_launches(ofl_eden_plan_t plan, int encode);
 int ofl_eden_plan_launch_info(ofl_eden_plan_t plan, int encode, int idx, char* name, int cap,

@@ -2,7 +2,8 @@
 
 This is the layer the plugin (openfl_amd.pipelines.eden_pipeline) and
 bench.py sit on.  A batch of tensors lives in one fp32 arena (tensor t at
-element offset ``plan.elem_offsets[t]``); its Eden bit planes live in one byte
+element offset ``plan.elem_offsets[t]``; encode and decode also take
+bfloat16 arenas of the same layout); its Eden bit planes live in one byte
 arena (tensor t at ``plan.planes_offsets[t]``, ``plan.planes_nbytes[t]``
 bytes, the reference's to_bits layout, eden_pipeline.py:661-690) and its
 per-slice scales in one float array (tensor t's slices start at
@@ -74,6 +75,7 @@ class EdenPlan:
                                           self.n_bits, ctypes.byref(h)))
         self._h = h
         self._L = L
+        self._side = {}  # (device, stream) -> the float32 side arena of the bf16 calls (_side_arena)
         if wave_mib is not None or streams is not None:
             _lib.check(L.ofl_eden_plan_set_schedule(h, -1 if wave_mib is None else int(float(wave_mib) * 2 ** 20),
                                                     0 if streams is None else int(streams)))
@@ -93,6 +95,7 @@ class EdenPlan:
         self.planes_bytes = int(L.ofl_eden_plan_planes_bytes(h))
         self.ws_bytes = int(L.ofl_eden_plan_workspace_bytes(h))
         self.roundtrip_ws_bytes = int(L.ofl_eden_roundtrip_workspace_bytes(h))
+        self.side_numel = int(L.ofl_eden_bf16_side_numel(h))  # float32 elements of the bf16 calls' side arena
         self.planes_offsets, self.planes_nbytes, self.first_slice, self.dims = [], [], [], []
         for t in range(nt):
             po, pb = ctypes.c_int64(), ctypes.c_int64()
@@ -118,29 +121,73 @@ class EdenPlan:
         return self._h
 
     # -- raw launches (all pointers are device tensors) --
+    def _side_arena(self, device, stream):
+        """The float32 scratch the slices of at most 2^15 elements go through
+        when the caller's arenas are bfloat16 (ofl_eden_encode_bf16): it
+        holds those slices' elements alone (side_numel of them, not
+        arena_numel), one per device and stream -- calls on one stream run in
+        order and may share it, calls on different streams may not -- made
+        on first use and kept with the plan; None for a plan without such a
+        slice."""
+        if not self.side_numel:
+            return None
+        key = (str(device), stream.cuda_stream)
+        if key not in self._side:
+            self._side[key] = torch.empty(self.side_numel, dtype=torch.float32, device=device)
+        return self._side[key]
+
+    def _check_arena(self, t, what):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.CodecError(f"{what} must be a torch.float32 or torch.bfloat16 arena, not {t.dtype}")
+        self._check(t, t.dtype, self.arena_numel)
+        return t.dtype == torch.bfloat16
+
     def encode(self, x_arena, seeds, planes, scales, ws, stream=None):
-        """x_arena fp32[arena_numel] -> planes u8[planes_bytes], scales f32[n_slices]."""
-        self._check(x_arena, torch.float32, self.arena_numel)
+        """x_arena fp32 or bf16 [arena_numel] -> planes u8[planes_bytes], scales
+        f32[n_slices]; a bf16 arena gives the planes and scales of its
+        float32 widening, read as bf16 (ofl_eden_encode_bf16)."""
+        bf16 = self._check_arena(x_arena, "x_arena")
         self._check(planes, torch.uint8, self.planes_bytes)
         self._check(scales, torch.float32, self.n_slices)
         self._check(seeds, torch.int32, len(self.numels))
         st = stream if stream is not None else torch.cuda.current_stream(x_arena.device)
+        if bf16:
+            side = self._side_arena(x_arena.device, st)
+            _lib.check(self._L.ofl_eden_encode_bf16(self._h, x_arena.data_ptr(),
+                                                    side.data_ptr() if side is not None else None, seeds.data_ptr(),
+                                                    planes.data_ptr(), scales.data_ptr(),
+                                                    ws.data_ptr() if ws is not None else None,
+                                                    ws.numel() if ws is not None else 0, st.cuda_stream))
+            return
         _lib.check(self._L.ofl_eden_encode(self._h, x_arena.data_ptr(), seeds.data_ptr(),
                                            planes.data_ptr(), scales.data_ptr(),
                                            ws.data_ptr() if ws is not None else None,
                                            ws.numel() if ws is not None else 0, st.cuda_stream))
 
     def decode(self, planes, seeds, scales, y_arena, ws, stream=None, base=None):
-        """planes u8 + scales f32 -> y_arena fp32 (numel[t] elements of each
-        tensor); with base (an arena of this layout): y = base + decoded
-        (TensorCodec.apply_delta fused, ofl_eden_decode_add)."""
-        self._check(y_arena, torch.float32, self.arena_numel)
+        """planes u8 + scales f32 -> y_arena fp32 or bf16 (numel[t] elements of
+        each tensor); with base (an arena of this layout and y_arena's
+        dtype): y = base + decoded (TensorCodec.apply_delta fused,
+        ofl_eden_decode_add).  A bf16 y_arena holds the float32 y rounded to
+        nearest even (ofl_eden_decode_add_bf16)."""
+        bf16 = self._check_arena(y_arena, "y_arena")
         self._check(planes, torch.uint8, self.planes_bytes)
         self._check(scales, torch.float32, self.n_slices)
         self._check(seeds, torch.int32, len(self.numels))
         if base is not None:
-            self._check(base, torch.float32, self.arena_numel)
+            if base.dtype != y_arena.dtype:
+                raise _lib.CodecError(f"base must have y_arena's dtype {y_arena.dtype}, not {base.dtype}")
+            self._check(base, y_arena.dtype, self.arena_numel)
         st = stream if stream is not None else torch.cuda.current_stream(y_arena.device)
+        if bf16:
+            side = self._side_arena(y_arena.device, st)
+            _lib.check(self._L.ofl_eden_decode_add_bf16(self._h, planes.data_ptr(), seeds.data_ptr(), scales.data_ptr(),
+                                                        base.data_ptr() if base is not None else None,
+                                                        y_arena.data_ptr(),
+                                                        side.data_ptr() if side is not None else None,
+                                                        ws.data_ptr() if ws is not None else None,
+                                                        ws.numel() if ws is not None else 0, st.cuda_stream))
+            return
         _lib.check(self._L.ofl_eden_decode_add(self._h, planes.data_ptr(), seeds.data_ptr(),
                                                scales.data_ptr(), base.data_ptr() if base is not None else None,
                                                y_arena.data_ptr(), ws.data_ptr() if ws is not None else None,
@@ -202,6 +249,12 @@ class EdenPlan:
         walks the paired tile table) and grid (workgroups launched)."""
         return self._launches(1 if encode else 0)
 
+    def bf16_launches(self, encode):
+        """The launches of an encode / decode with bfloat16 arenas, as
+        launches() reports them (the small slices' two range launches, which
+        are not the plan's, are not listed)."""
+        return self._launches(4 if encode else 5)
+
     def roundtrip_launches(self):
         """The launches of a plain round trip, as launches() reports them."""
         return self._launches(2)
@@ -224,8 +277,9 @@ class EdenPlan:
 
     def profile_collect(self, encode):
         """-> (per-launch summed ms, number of recorded calls).  encode: False
-        / True, 2 for the round trip's launches, 3 for decode_accumulate's."""
-        which = int(encode) if encode in (2, 3) else 1 if encode else 0
+        / True, 2 for the round trip's launches, 3 for decode_accumulate's,
+        4 / 5 for encode's / decode's with bfloat16 arenas."""
+        which = int(encode) if encode in (2, 3, 4, 5) else 1 if encode else 0
         n = self._L.ofl_eden_plan_num_launches(self._h, which)
         ms = np.zeros(max(n, 1), np.float64)
         calls = ctypes.c_int()
@@ -410,6 +464,7 @@ class EdenCodec:
 
     encode(list of fp32 device tensors, seeds) -> (planes u8, scales f32, plan)
     decode(planes, scales, seeds, plan) -> fp32 arena (slice per tensor with plan).
+    encode_arena / decode_arena take float32 or bfloat16 arenas.
     """
 
     def __init__(self, n_bits=8, device=None, max_plans=256):
@@ -448,11 +503,12 @@ class EdenCodec:
         plan.encode(x_arena, seeds_dev, planes, scales, ws, stream)
         return planes, scales
 
-    def decode_arena(self, plan, planes, scales, seeds_dev, stream=None, out=None):
-        y = out if out is not None else torch.empty(max(plan.arena_numel, 1), dtype=torch.float32,
-                                                    device=self.device)
+    def decode_arena(self, plan, planes, scales, seeds_dev, stream=None, out=None, dtype=torch.float32, base=None):
+        """-> y: `out`, or a new arena of `dtype` (float32 or bfloat16); with
+        base (an arena of y's dtype): y = base + decoded (EdenPlan.decode)."""
+        y = out if out is not None else torch.empty(max(plan.arena_numel, 1), dtype=dtype, device=self.device)
         ws = self.ws.get(plan.ws_bytes, self.device)
-        plan.decode(planes, seeds_dev, scales, y, ws, stream)
+        plan.decode(planes, seeds_dev, scales, y, ws, stream, base=base)
         return y
 
     def roundtrip_arena(self, plan, x_arena, seeds_dev, out=None, base=None):

@@ -56,6 +56,7 @@
 #include "eden_plan.h"
 #include "eden_rt_plan.h"
 #include "eden_acc_plan.h"
+#include "eden_bf16_plan.h"
 #include "eden_tables.h"
 #include "lds_exchange.h"
 #include "ofl_codec.h"
@@ -111,20 +112,30 @@ struct KArgs {
     union {
         uint8_t* pout;      // planes out (encode)
         double* sums;       // the sums arena (decode-accumulate)
+        uint16_t* y16;      // the bf16 arena out (ofl_eden_decode_add_bf16, eden_bf16.h)
     };
     const uint32_t* seeds;
     float* scales;          // encode: out
     const float* scales_in; // decode: in
     float* part;            // partial sums
     float* nu;              // per-slice norms (large)
-    const float* yadd;      // decode: nullable, y = yadd + decoded (apply_delta, float32 add)
+    // the bf16 arenas (eden_bf16.h) share places their direction leaves free:
+    // encode reads x16 where decode has yadd, decode reads base16 where the
+    // weighted-average encode has wbase and writes y16 where encode has pout
+    union {
+        const float* yadd;      // decode: nullable, y = yadd + decoded (apply_delta, float32 add)
+        const uint16_t* x16;    // bf16 encode: the arena in (large slices; xin is the float32 side arena)
+    };
     const int32_t* btab;    // column launches: per block {slice, tile << 3 | group} (nullable)
     // round-end fused encode (ofl_eden_encode_wavg): the large slices' x is
     // the float32-rounded delta (sum_c f64(x_c) * w_c) / wsum - f64(base),
     // computed from the collaborators' arenas as the row pass loads it
     const float* const* wx; // collaborator arenas (device array of wc pointers), nullable
     const double* ww;       // their weights (device)
-    const float* wbase;     // base model arena, nullable
+    union {
+        const float* wbase;     // base model arena, nullable
+        const uint16_t* base16; // bf16 decode: nullable, y16 = bf16(base16 + decoded)
+    };
     union {
         double wsum;        // NumPy's float64 sum of the weights
         double acc_w;       // the collaborator's weight (decode-accumulate)
@@ -1342,6 +1353,7 @@ DEVI void fetch_planes(const KArgs& a, const SliceDesc& D, uint32_t tile, bool l
 }
 
 // encode pass A: x -> D1 -> F1 row stages -> ws ; partial sum of x^2
+// (k_enc_rowA_bf16 in eden_bf16.h is this kernel with another prologue: a change here belongs there too)
 __global__ __launch_bounds__(kRowNT) void k_enc_rowA(KArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* s = reinterpret_cast<float*>(smem);
@@ -1421,6 +1433,8 @@ __global__ __launch_bounds__(kRowNT) void k_dec_rowA(KArgs a) {
 }
 
 // decode pass C: ws -> G2 row stages -> D1, scale -> y
+// (k_dec_acc_rowC in eden_dec_acc.h and k_dec_rowC_bf16 in eden_bf16.h are this
+// kernel with another epilogue: a change here belongs there too)
 __global__ __launch_bounds__(kRowNT) void k_dec_rowC(KArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* s = reinterpret_cast<float*>(smem);
@@ -2175,6 +2189,7 @@ DEVI void fetch_x_wavg(const KArgs& a, const SliceDesc& D, uint32_t tile, uint32
 }
 
 // encode pass A (as k_enc_rowA); WAVG: x from the collaborators' arenas
+// (k_enc_rowA2_bf16 in eden_bf16.h is <false> with another prologue: a change here belongs there too)
 template <bool WAVG>
 __global__ __launch_bounds__(kRowNT, 4) void k_enc_rowA2(KArgs a) {
     using R = RowA2Set;
@@ -2260,7 +2275,8 @@ __global__ __launch_bounds__(kRowNT, 4) void k_dec_rowA2(KArgs a) {
     }
 }
 
-// decode pass C (as k_dec_rowC)
+// decode pass C (as k_dec_rowC; k_dec_acc_rowC2 in eden_dec_acc.h and k_dec_rowC2_bf16
+// in eden_bf16.h are this kernel with another epilogue: a change here belongs there too)
 __global__ __launch_bounds__(kRowNT, 4) void k_dec_rowC2(KArgs a) {
     using R = DecC2Set;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2322,6 +2338,8 @@ __global__ __launch_bounds__(256) void k_finalize(KArgs a) {
 #include "eden_rt_row.h"
 // decode's last row pass into the streaming average's sums, after it
 #include "eden_dec_acc.h"
+// the row passes' bf16 arena I/O and the small slices' widen / narrow, after it
+#include "eden_bf16.h"
 
 }  // namespace ofl
 
@@ -2348,11 +2366,18 @@ struct ofl_eden_plan {
     const char* rt_err = nullptr;  // why the plan has none (ofl_eden_roundtrip reports it)
     // profiling: events around every launch of every call while enabled
     bool prof = false;
-    std::vector<std::vector<hipEvent_t>> prof_ev[4];  // [dec, enc, round trip, decode-accumulate][call][launch+1]
+    std::vector<std::vector<hipEvent_t>> prof_ev[6];  // [dec, enc, round trip, decode-accumulate, bf16 enc, bf16 dec][call][launch+1]
     std::vector<hipEvent_t> ev_pool;
     ofl::SliceDesc* d_slices = nullptr;
     ofl::SliceDesc* d_rt_slices = nullptr;  // rt.slices
     int32_t* d_ints = nullptr;
+    // the small slices' input / output ranges (eden::small_ranges) and the
+    // slice table that places those slices in the side arena
+    // (eden::bf16_slices), made and uploaded by the first call with bf16 arenas
+    eden::SmallRanges rg16[2];
+    int64_t* d_rg16[2] = {nullptr, nullptr};
+    ofl::SliceDesc* d_slices16 = nullptr;
+    bool rg16_ready = false;
     int device = -1;
     int ncu = 256;              // persistent row launches: one block per CU (eden::resolve)
     bool uploaded = false;
@@ -2440,10 +2465,19 @@ constexpr KernelEntry kAccKernels[eden::ACC_KERNEL_COUNT] = {
     {eden::KERNEL_COUNT, ofl::k_dec_acc_rowC2, ofl::kRowNT, ofl::kRow2Smem},
 };
 
+// the bf16 arenas' own kernels, one entry per eden::Bf16KernelId (the LDS of the kernels they stand in for)
+constexpr KernelEntry kBf16Kernels[eden::BF16_KERNEL_COUNT] = {
+    {eden::KERNEL_COUNT, ofl::k_enc_rowA_bf16, ofl::kRowNT, ofl::kRowSmemA},
+    {eden::KERNEL_COUNT, ofl::k_enc_rowA2_bf16, ofl::kRowNT, ofl::kRow2Smem},
+    {eden::KERNEL_COUNT, ofl::k_dec_rowC_bf16, ofl::kRowNT, ofl::kRowSmemA},
+    {eden::KERNEL_COUNT, ofl::k_dec_rowC2_bf16, ofl::kRowNT, ofl::kRow2Smem},
+};
+
 hipError_t set_all_attrs() {
     const std::pair<const KernelEntry*, int> tabs[] = {{kKernels, (int)eden::KERNEL_COUNT},
                                                        {kRtKernels, (int)eden::RT_KERNEL_COUNT},
-                                                       {kAccKernels, (int)eden::ACC_KERNEL_COUNT}};
+                                                       {kAccKernels, (int)eden::ACC_KERNEL_COUNT},
+                                                       {kBf16Kernels, (int)eden::BF16_KERNEL_COUNT}};
     for (const auto& [tab, n] : tabs)
         for (int i = 0; i < n; ++i) {
             const KernelEntry& k = tab[i];
@@ -2455,24 +2489,29 @@ hipError_t set_all_attrs() {
 }
 
 // which of a plan's launch lists a call runs (the ABI's `encode` argument)
-enum { RUN_DEC = 0, RUN_ENC = 1, RUN_RT = 2, RUN_ACC = 3, RUN_COUNT };
+enum { RUN_DEC = 0, RUN_ENC = 1, RUN_RT = 2, RUN_ACC = 3, RUN_ENC16 = 4, RUN_DEC16 = 5, RUN_COUNT };
 int num_launches(const ofl_eden_plan* pl, int which) {
-    return (int)(which == RUN_RT ? pl->rt.list.size() : which == RUN_ENC ? pl->p.enc.size() : pl->p.dec.size());
+    const bool enc = which == RUN_ENC || which == RUN_ENC16;
+    return (int)(which == RUN_RT ? pl->rt.list.size() : enc ? pl->p.enc.size() : pl->p.dec.size());
 }
 // launch idx of a list and what it runs (ncu CUs; wavg: the weighted-average
-// first pass; planes8: eden::resolve): kKernels[r.id], or the round trip's or
-// decode-accumulate's own kernel in its place
+// first pass; planes8: eden::resolve): kKernels[r.id], or the round trip's,
+// decode-accumulate's or the bf16 arenas' own kernel in its place
 struct Picked {
     const Launch* l;
     eden::Resolved r;
     const KernelEntry* k;
     const char* name;
     bool acc;  // a decode-accumulate row launch (its bytes: eden::acc_bytes_moved)
+    bool bf;   // a row launch on a bf16 arena (its bytes: eden::bf16_bytes_moved / _alg)
 };
 const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, bool wavg, bool planes8, Picked& p) {
     const char* err = nullptr;
-    int rt = -1, acc = -1;
-    if (which == RUN_RT) {
+    int rt = -1, acc = -1, bf = -1;
+    if (which == RUN_ENC16 || which == RUN_DEC16) {
+        p.l = &(which == RUN_ENC16 ? pl->p.enc : pl->p.dec)[idx];
+        err = eden::bf16_resolve(pl->p, *p.l, which == RUN_ENC16, ncu, planes8, p.r, bf);
+    } else if (which == RUN_RT) {
         eden::RtResolved x;
         p.l = &pl->rt.list[idx].l;
         err = eden::rt_resolve(pl->p, pl->rt.list[idx], ncu, wavg, x);
@@ -2487,8 +2526,10 @@ const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, boo
     }
     if (err) return err;
     p.acc = acc >= 0;
-    p.k = rt >= 0 ? &kRtKernels[rt] : acc >= 0 ? &kAccKernels[acc] : &kKernels[p.r.id];
-    p.name = rt >= 0 ? eden::kRtKernelName[rt] : acc >= 0 ? eden::kAccKernelName[acc] : eden::kKernelName[p.r.id];
+    p.bf = bf >= 0;
+    p.k = rt >= 0 ? &kRtKernels[rt] : acc >= 0 ? &kAccKernels[acc] : bf >= 0 ? &kBf16Kernels[bf] : &kKernels[p.r.id];
+    p.name = rt >= 0 ? eden::kRtKernelName[rt] : acc >= 0 ? eden::kAccKernelName[acc]
+             : bf >= 0 ? eden::kBf16KernelName[bf] : eden::kKernelName[p.r.id];
     return nullptr;
 }
 
@@ -2730,6 +2771,9 @@ void ofl_eden_plan_destroy(ofl_eden_plan_t pl) {
     if (pl->d_slices) (void)hipFree(pl->d_slices);
     if (pl->d_rt_slices) (void)hipFree(pl->d_rt_slices);
     if (pl->d_ints) (void)hipFree(pl->d_ints);
+    for (int64_t* d : pl->d_rg16)
+        if (d) (void)hipFree(d);
+    if (pl->d_slices16) (void)hipFree(pl->d_slices16);
     if (pl->ev_join2) (void)hipEventDestroy(pl->ev_join2);
     if (pl->ev_fork) (void)hipEventDestroy(pl->ev_fork);
     if (pl->ev_join) (void)hipEventDestroy(pl->ev_join);
@@ -2867,6 +2911,92 @@ int ofl_eden_decode_accumulate(ofl_eden_plan_t pl, const uint8_t* planes_arena, 
     a.acc_w = w;
     a.acc_first = first ? 1 : 0;
     return run(pl, RUN_ACC, a, static_cast<hipStream_t>(stream));
+}
+
+// The small slices' range tables and the bf16 calls' slice table on the
+// device, on the first call with bf16 arenas (one synchronous copy each, as
+// ensure_device's: not inside a graph capture), and what every such call
+// checks before it launches anything
+static int prep_bf16(ofl_eden_plan_t pl, const char* what, const void* arena16, const void* base16, const void* side) {
+    const std::string w(what);
+    if ((reinterpret_cast<uintptr_t>(arena16) | reinterpret_cast<uintptr_t>(base16)) & 7u || !eden::bf16_aligned(pl->p))
+        return fail(OFL_EINVAL, w + ": bf16 arenas must be 8-byte aligned, with tensor offsets that are multiples of 4");
+    if (!side && eden::has_small_slice(pl->p))
+        return fail(OFL_EINVAL, w + ": the plan has slices of at most 2^15 elements, which need the float32 side arena");
+    if (reinterpret_cast<uintptr_t>(side) & 15u) return fail(OFL_EINVAL, w + ": the side arena must be 16-byte aligned");
+    if (int rc = ensure_device(pl)) return rc;
+    std::lock_guard<std::mutex> g(pl->mu);
+    if (pl->rg16_ready) return OFL_OK;
+    for (int o = 0; o < 2; ++o) {
+        pl->rg16[o] = eden::small_ranges(pl->p, o == 1);
+        const size_t bytes = sizeof(int64_t) * pl->rg16[o].tab.size();
+        if (!pl->d_rg16[o]) HIP_TRY(hipMalloc(&pl->d_rg16[o], bytes));
+        HIP_TRY(hipMemcpy(pl->d_rg16[o], pl->rg16[o].tab.data(), bytes, hipMemcpyHostToDevice));
+    }
+    if (!pl->p.slices.empty()) {
+        const std::vector<ofl::SliceDesc> sl = eden::bf16_slices(pl->p, pl->rg16[0], pl->rg16[1]);
+        if (!pl->d_slices16) HIP_TRY(hipMalloc(&pl->d_slices16, sizeof(ofl::SliceDesc) * sl.size()));
+        HIP_TRY(hipMemcpy(pl->d_slices16, sl.data(), sizeof(ofl::SliceDesc) * sl.size(), hipMemcpyHostToDevice));
+    }
+    pl->rg16_ready = true;
+    return OFL_OK;
+}
+// the grid of a range launch over `slots` slots (grid-stride above the cap)
+static unsigned range_grid(int64_t slots) {
+    return (unsigned)std::min<int64_t>((slots + ofl::kRangeNT - 1) / ofl::kRangeNT, 8192);
+}
+
+int64_t ofl_eden_bf16_side_numel(ofl_eden_plan_t pl) { return pl ? eden::bf16_side_numel(pl->p) : -1; }
+
+int ofl_eden_encode_bf16(ofl_eden_plan_t pl, const uint16_t* x_arena, float* x_small, const uint32_t* seeds,
+                         uint8_t* planes_arena, float* scales, void* ws, size_t ws_bytes, void* stream) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    if (!x_arena || !seeds || !planes_arena || !scales) return fail(OFL_EINVAL, "encode_bf16: null argument");
+    if (int rc = prep_bf16(pl, "encode_bf16", x_arena, nullptr, x_small)) return rc;
+    ofl::KArgs a;
+    if (int rc = prep_args(pl, a, ws, ws_bytes)) return rc;
+    a.d = pl->d_slices16;  // the tiny / small slices in the side arena
+    a.xin = x_small;       // their encode kernels alone read it
+    a.x16 = x_arena;
+    a.pout = planes_arena;
+    a.seeds = seeds;
+    a.scales = scales;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const eden::SmallRanges& R = pl->rg16[0];
+    if (R.slots > 0) {
+        const int vec = 1;  // prep_bf16: both arenas are aligned for the 8- and 16-byte accesses
+        hipLaunchKernelGGL(ofl::k_widen_ranges, dim3(range_grid(R.slots)), dim3(ofl::kRangeNT), 0, st, x_arena, x_small,
+                           ofl::QRanges{pl->d_rg16[0], R.nr}, vec);
+        HIP_TRY(hipGetLastError());
+    }
+    return run(pl, RUN_ENC16, a, st);
+}
+
+int ofl_eden_decode_add_bf16(ofl_eden_plan_t pl, const uint8_t* planes_arena, const uint32_t* seeds, const float* scales,
+                             const uint16_t* base_arena, uint16_t* y_arena, float* y_small, void* ws, size_t ws_bytes,
+                             void* stream) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    if (!planes_arena || !seeds || !scales || !y_arena) return fail(OFL_EINVAL, "decode_add_bf16: null argument");
+    if (int rc = prep_bf16(pl, "decode_add_bf16", y_arena, base_arena, y_small)) return rc;
+    ofl::KArgs a;
+    if (int rc = prep_args(pl, a, ws, ws_bytes)) return rc;
+    a.pin = planes_arena;
+    a.d = pl->d_slices16;  // the tiny / small slices in the side arena
+    a.xout = y_small;      // their decode kernels alone write it: decoded, no base (yadd stays null)
+    a.y16 = y_arena;
+    a.base16 = base_arena;
+    a.seeds = seeds;
+    a.scales_in = scales;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = run(pl, RUN_DEC16, a, st)) return rc;
+    const eden::SmallRanges& R = pl->rg16[1];
+    if (R.slots > 0) {
+        const int vec = 1;  // as in ofl_eden_encode_bf16
+        hipLaunchKernelGGL(ofl::k_narrow_ranges, dim3(range_grid(R.slots)), dim3(ofl::kRangeNT), 0, st,
+                           static_cast<const float*>(y_small), base_arena, y_arena, ofl::QRanges{pl->d_rg16[1], R.nr}, vec);
+        HIP_TRY(hipGetLastError());
+    }
+    return OFL_OK;
 }
 
 int64_t ofl_eden_roundtrip_workspace_bytes(ofl_eden_plan_t pl) {
@@ -3163,8 +3293,8 @@ int ofl_eden_plan_launch_info(ofl_eden_plan_t pl, int encode, int idx, char* nam
     if (int rc = resolve_plain(pl, encode, idx, p)) return rc;
     if (name && cap > 0) snprintf(name, (size_t)cap, "%s", p.name);
     if (blocks) *blocks = p.l->blocks;
-    if (bytes_moved) *bytes_moved = p.acc ? eden::acc_bytes_moved(*p.l) : p.l->bytes_moved;
-    if (bytes_alg) *bytes_alg = p.acc ? 0 : p.l->bytes_alg;
+    if (bytes_moved) *bytes_moved = p.acc ? eden::acc_bytes_moved(*p.l) : p.bf ? eden::bf16_bytes_moved(*p.l) : p.l->bytes_moved;
+    if (bytes_alg) *bytes_alg = p.acc ? 0 : p.bf ? eden::bf16_bytes_alg(*p.l) : p.l->bytes_alg;
     return OFL_OK;
 }
 
