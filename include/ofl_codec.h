@@ -236,6 +236,47 @@ int ofl_eden_encode_bf16(ofl_eden_plan_t plan, const uint16_t* x_arena, float* x
 int ofl_eden_decode_add_bf16(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uint32_t* seeds,
                              const float* scales, const uint16_t* base_arena /* nullable */, uint16_t* y_arena,
                              float* y_small, void* ws, size_t ws_bytes, void* stream);
+/* ofl_eden_decode_accumulate against a bfloat16 base (uint16_t, the plan's
+ * layout, 2 bytes per element; nullable).  A bf16 base stands for its exact
+ * float32 widening and nothing is rounded to bf16: per element i below the
+ * tensor's length
+ *     x = base16 ? float32(widen(base16[i]) + decoded[i]) : decoded[i]
+ *     sums[i] = first ? (double)x * w : sums[i] + (double)x * w
+ * i.e. ofl_eden_decode_accumulate's sums on the widened base, bit for bit (a
+ * first product of -0.0 is stored as -0.0).  The plan's decode schedule runs as
+ * it is -- the same waves, streams, fork / join and workspace -- with
+ * k_dec_acc_rowC_bf16 / k_dec_acc_rowC2_bf16 as the last row pass of the
+ * slices above 2^15 elements: a quad's base is one 8-byte load, so the pass
+ * moves 22 instead of 24 bytes per element.  Slices of at most 2^15 elements
+ * keep their decode kernels and write y_side, the packed float32 side arena
+ * of ofl_eden_bf16_side_numel() elements (16-byte aligned; NULL when that is
+ * 0; scratch of the call, as in ofl_eden_decode_add_bf16); the call folds it
+ * into the sums itself, base added, with one k_acc_side_ranges launch on
+ * `stream` after the decode -- unlike ofl_eden_decode_accumulate, which leaves
+ * its y_small to the caller.  Nothing of sums outside the tensors' elements
+ * is read or written, and nothing of base16 at or past a tensor's length is
+ * read.  base16 8-byte and sums 16-byte aligned, tensor offsets multiples of
+ * 4 elements.  A null planes / seeds / scales / sums, a misaligned base or
+ * sums, or a missing or misaligned side arena: OFL_EINVAL, nothing launched.
+ * Async on `stream` and graph-capturable after the plan's first call with
+ * bf16 arenas.
+ * ofl_acc_side_ranges  the fold of a packed float32 buffer by itself, for
+ *     what the codec does not touch (an upload's raw tensors): table_dev is
+ *     a DEVICE table of int64 s[nranges] | e[nranges] | dst[nranges + 1] --
+ *     element ranges [s, e) of the arena, walked in slots of 4 elements at
+ *     arena indices that are multiples of 4, dst the exclusive prefix of the
+ *     ranges' slot counts (dst[nranges] = slots); arena element i of range r
+ *     is side[4 * (dst[r] + (i >> 2) - (s[r] >> 2)) + (i & 3)].  Per element
+ *     sums[i] (=|+=) (double)(base16 ? float32(widen(base16[i]) + side[c]) :
+ *     side[c]) * w.  Whole slots move 16 + 8 + 32 + 32 bytes in 16- / 8-byte
+ *     accesses where side and sums are 16-byte and base16 8-byte aligned;
+ *     otherwise, and in a range's ragged first and last slot, element by
+ *     element.  nranges < 1 or slots <= 0: nothing to do. */
+int ofl_eden_decode_accumulate_bf16(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uint32_t* seeds,
+                                    const float* scales, const uint16_t* base16 /* nullable */, double w, int first,
+                                    double* sums, float* y_side, void* ws, size_t ws_bytes, void* stream);
+int ofl_acc_side_ranges(const float* side, const uint16_t* base16 /* nullable */, double w, int first, double* sums,
+                        const int64_t* table_dev, int nranges, int64_t slots, void* stream);
 /* The round trip y = decode(encode(x)) (+ base when given) with the bytes
  * discarded: what Aggregator._prepare_trained computes when nothing is sent
  * (aggregator.py:816-826), and the y of a collaborator's error feedback
@@ -340,7 +381,10 @@ int ofl_side_stream(int index, void** stream);
  * 4 encode from and 5 decode into bf16 arenas (ofl_eden_encode_bf16 /
  * ofl_eden_decode_add_bf16: the plan's launches, the first / last row passes
  * under their own names with 2 arena bytes per element instead of 4; the two
- * range launches of the small slices' side arena are not listed). */
+ * range launches of the small slices' side arena are not listed), 6 decode
+ * into the sums against a bf16 base (ofl_eden_decode_accumulate_bf16: list
+ * 3 with the row passes' bf16 names and a 2-byte base; the side arena's fold
+ * is not listed). */
 int ofl_eden_plan_profile(ofl_eden_plan_t plan, int enable);
 int ofl_eden_plan_num_launches(ofl_eden_plan_t plan, int encode);
 int ofl_eden_plan_launch_info(ofl_eden_plan_t plan, int encode, int idx, char* name, int cap,
@@ -522,6 +566,30 @@ int ofl_wavg_delta(int ncollab, const float* const* xs, const double* weights, d
 int ofl_wavg_accumulate(const float* x, double w, int first, int64_t n, double* sums, void* stream);
 int ofl_wavg_finish(double* sums, double wsum, const float* base, int64_t n, double* delta64_out, float* delta32_out,
                     void* stream);
+/* The round on bfloat16 model arenas (uint16_t, 2 bytes per element): a bf16
+ * arena stands for its exact float32 widening, so each call below gives the
+ * bits of its float32 form on the widened arena; only ofl_apply_delta_ranges_bf16
+ * rounds, once, to nearest even.  8-byte accesses of the bf16 arena where every
+ * arena of the call is aligned for its 4-element access, else element by element.
+ * ofl_wavg_accumulate_bf16   ofl_wavg_accumulate with widen(x16[i]) for x[i].
+ *                 Reads 2 + 8, writes 8 bytes/element.
+ * ofl_wavg_finish_bf16       ofl_wavg_finish with widen(base16[i]) for base[i]
+ *                 (base16 may be NULL).  Reads 8 + 2, writes 8 + 4.
+ * ofl_agg_delta_seeds_bf16   ofl_agg_delta_seeds of a float64 aggregate with
+ *                 delta = agg - (double)widen(base16[i]); the same ranges,
+ *                 left-to-right float64 sums and hash.  base16 may be NULL.
+ * ofl_apply_delta_ranges_bf16   on the listed ranges (tables as
+ *                 ofl_apply_delta_ranges) out16[i] = bf16(float32(widen(base16[i])
+ *                 + delta32[i])): the raw tensors of a round's tail.  delta32
+ *                 is a whole float32 arena; out16 may alias base16. */
+int ofl_wavg_accumulate_bf16(const uint16_t* x16, double w, int first, int64_t n, double* sums, void* stream);
+int ofl_wavg_finish_bf16(double* sums, double wsum, const uint16_t* base16, int64_t n, double* delta64_out,
+                         float* delta32_out, void* stream);
+int ofl_agg_delta_seeds_bf16(const double* agg_dev, const uint16_t* base16, int nranges, const int64_t* starts_dev,
+                             const int64_t* dst_dev, int64_t total, const int64_t* draws_dev, uint32_t* seeds_dev,
+                             double* sums_dev, double* packed_dev, void* stream);
+int ofl_apply_delta_ranges_bf16(const uint16_t* base16, const float* delta32, uint16_t* out16, int nranges,
+                                const int64_t* starts, const int64_t* dst, int64_t total, void* stream);
 /* ofl_wavg_delta_seeds  the Eden seeds of a round end without a host round
  *                 trip: the float64 delta on the listed ranges (packed_dev,
  *                 total doubles; single_dev[r] != 0: a single-element tensor,

@@ -22,7 +22,7 @@ EXPORTS = (
     "ofl_eden_plan_destroy", "ofl_eden_plan_set_schedule", "ofl_eden_plan_num_waves",
     "ofl_eden_plan_get_schedule", "ofl_eden_plan_set_row2", "ofl_eden_plan_set_pair", "ofl_eden_plan_set_sset", "ofl_eden_plan_set_fuse", "ofl_eden_plan_num_slices", "ofl_eden_plan_planes_bytes",
     "ofl_eden_plan_workspace_bytes", "ofl_eden_plan_tensor_info", "ofl_eden_plan_tensor_dims",
-    "ofl_eden_encode", "ofl_eden_encode_wavg", "ofl_eden_decode", "ofl_eden_decode_add", "ofl_eden_decode_accumulate", "ofl_eden_bf16_side_numel", "ofl_eden_encode_bf16", "ofl_eden_decode_add_bf16", "ofl_eden_roundtrip", "ofl_eden_roundtrip_wavg", "ofl_eden_roundtrip_workspace_bytes", "ofl_eden_encode_host", "ofl_eden_decode_host", "ofl_eden_encode_mapped", "ofl_eden_decode_mapped", "ofl_eden_encode_seeded", "ofl_copy_h2d_chunked", "ofl_eden_encode_host_x", "ofl_eden_decode_host_x", "ofl_copy_h2d_async", "ofl_copy_h2d_staged", "ofl_eden_plan_profile", "ofl_eden_plan_num_launches",
+    "ofl_eden_encode", "ofl_eden_encode_wavg", "ofl_eden_decode", "ofl_eden_decode_add", "ofl_eden_decode_accumulate", "ofl_eden_bf16_side_numel", "ofl_eden_encode_bf16", "ofl_eden_decode_add_bf16", "ofl_eden_decode_accumulate_bf16", "ofl_acc_side_ranges", "ofl_eden_roundtrip", "ofl_eden_roundtrip_wavg", "ofl_eden_roundtrip_workspace_bytes", "ofl_eden_encode_host", "ofl_eden_decode_host", "ofl_eden_encode_mapped", "ofl_eden_decode_mapped", "ofl_eden_encode_seeded", "ofl_copy_h2d_chunked", "ofl_eden_encode_host_x", "ofl_eden_decode_host_x", "ofl_copy_h2d_async", "ofl_copy_h2d_staged", "ofl_eden_plan_profile", "ofl_eden_plan_num_launches",
     "ofl_eden_plan_launch_info", "ofl_eden_plan_launch_detail", "ofl_eden_plan_profile_collect", "ofl_serial_sum_f32", "ofl_serial_sum_f32_mt", "ofl_serial_sum_copy_f32",
     "ofl_serial_sum_f64", "ofl_host_copy_many", "ofl_serial_sums_many", "ofl_lossy_last_error", "ofl_lossy_workspace_bytes", "ofl_kmeans1d_fit",
     "ofl_kmeans1d_batch_workspace_bytes", "ofl_kmeans1d_batch", "ofl_kmeans1d_batch_tab",
@@ -30,7 +30,8 @@ EXPORTS = (
     "ofl_lut_decode_batch_workspace_bytes", "ofl_lut_decode_batch",
     "ofl_sparsify_topk_batch_workspace_bytes", "ofl_sparsify_topk_batch",
     "ofl_ternary_ranks_batch_workspace_bytes", "ofl_ternary_ranks_batch",
-    "ofl_agg_last_error", "ofl_wavg_delta", "ofl_wavg_accumulate", "ofl_wavg_finish", "ofl_wavg_delta_seeds", "ofl_py_hash_doubles",
+    "ofl_agg_last_error", "ofl_wavg_delta", "ofl_wavg_accumulate", "ofl_wavg_finish", "ofl_wavg_accumulate_bf16", "ofl_wavg_finish_bf16",
+    "ofl_agg_delta_seeds_bf16", "ofl_apply_delta_ranges_bf16", "ofl_wavg_delta_seeds", "ofl_py_hash_doubles",
     "ofl_wavg_points_workspace_bytes", "ofl_wavg_delta_points", "ofl_apply_delta",
     "ofl_apply_delta_ranges", "ofl_wavg_delta32_ranges", "ofl_wavg_accumulate_ranges", "ofl_sub_f32_f64",
     "ofl_median_delta", "ofl_gmedian_workspace_bytes", "ofl_gmedian_delta", "ofl_agg_delta_seeds",
@@ -94,6 +95,10 @@ def _bind(L):
     L.ofl_eden_encode_bf16.restype = i32
     L.ofl_eden_decode_add_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.ofl_eden_decode_add_bf16.restype = i32
+    L.ofl_eden_decode_accumulate_bf16.argtypes = [vp, vp, vp, vp, vp, ctypes.c_double, i32, vp, vp, vp, sz, vp]
+    L.ofl_eden_decode_accumulate_bf16.restype = i32
+    L.ofl_acc_side_ranges.argtypes = [vp, vp, ctypes.c_double, i32, vp, vp, i32, i64, vp]
+    L.ofl_acc_side_ranges.restype = i32
     L.ofl_eden_roundtrip_workspace_bytes.argtypes = [vp]
     L.ofl_eden_roundtrip_workspace_bytes.restype = i64
     L.ofl_eden_roundtrip.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp]
@@ -178,6 +183,14 @@ def _bind(L):
     L.ofl_wavg_accumulate.restype = i32
     L.ofl_wavg_finish.argtypes = [vp, ctypes.c_double, vp, i64, vp, vp, vp]
     L.ofl_wavg_finish.restype = i32
+    L.ofl_wavg_accumulate_bf16.argtypes = [vp, ctypes.c_double, i32, i64, vp, vp]
+    L.ofl_wavg_accumulate_bf16.restype = i32
+    L.ofl_wavg_finish_bf16.argtypes = [vp, ctypes.c_double, vp, i64, vp, vp, vp]
+    L.ofl_wavg_finish_bf16.restype = i32
+    L.ofl_agg_delta_seeds_bf16.argtypes = [vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.ofl_agg_delta_seeds_bf16.restype = i32
+    L.ofl_apply_delta_ranges_bf16.argtypes = [vp, vp, vp, i32, vp, vp, i64, vp]
+    L.ofl_apply_delta_ranges_bf16.restype = i32
     L.ofl_wavg_delta_seeds.argtypes = [i32, vp, vp, ctypes.c_double, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.ofl_wavg_delta_seeds.restype = i32
     L.ofl_py_hash_doubles.argtypes = [vp, i32, vp, vp]

@@ -697,18 +697,23 @@ class WavgAccumulator:
         return self._table[c]
 
     def add(self, arena, weight):
-        """Fold one collaborator in: arena (this layout, float32, on the
-        device; free to reuse once the current stream has passed this call)
-        and its weight (as run() takes them, not normalised)."""
+        """Fold one collaborator in: arena (this layout, float32 or -- with
+        an Eden pipeline -- bfloat16, on the device; free to reuse once the
+        current stream has passed this call) and its weight (as run() takes
+        them, not normalised).  A bfloat16 arena gives the sums of its float32
+        widening, read as bf16 (ofl_wavg_accumulate_bf16)."""
         re = self.re
         if self.finished:
             raise _lib.CodecError("accumulator: add() after finish()")
-        re._check_arena(arena)
+        bf16 = re._check_arena(arena, bf16=re._lossy is None)
         w, c = self._next_weight(weight)
+        fold = _lib.lib().ofl_wavg_accumulate_bf16 if bf16 else _lib.lib().ofl_wavg_accumulate
         with torch.cuda.device(re.device):
-            _lib.check_agg(_lib.lib().ofl_wavg_accumulate(arena.data_ptr(), w, 1 if c == 0 else 0, re.arena_numel,
-                                                          self.sums.data_ptr(), _stream(re.device)))
-            if re.single:
+            _lib.check_agg(fold(arena.data_ptr(), w, 1 if c == 0 else 0, re.arena_numel, self.sums.data_ptr(),
+                                _stream(re.device)))
+            if re.single and bf16:
+                self._row(c).copy_(arena.index_select(0, re._single_idx))   # widened
+            elif re.single:
                 torch.index_select(arena, 0, re._single_idx, out=self._row(c))
         self.weights.append(weight)
 
@@ -737,11 +742,21 @@ class WavgAccumulator:
         through the scratch and one ofl_wavg_accumulate_ranges.  The sums'
         bits on every tensor are the unfused path's.  CodecError where that
         does not apply.  fused=None (default): fused where it applies.  Every
-        check of ingest() and add() raises before anything is launched."""
+        check of ingest() and add() raises before anything is launched.
+        A bfloat16 base_arena (an Eden pipeline's lossy_compressed upload;
+        with delta=False it only selects this route) is always fused and stands
+        for its float32 widening: the slices above 2^15 elements fold against
+        the bf16 base in the row pass (ofl_eden_decode_accumulate_bf16), the
+        smaller slices and the raw tensors through two packed float32 buffers
+        (k_acc_side_ranges), the same sums bit for bit, and no float32 buffer
+        of arena size exists: the scratch arena is not made.  fused=False
+        raises CodecError then (ingest() does not take bfloat16)."""
         if self.finished:
             raise _lib.CodecError("accumulator: add_upload() after finish()")
         re = self.re
         dev = resolve_device(getattr(re, "device", None))
+        if base_arena is not None and base_arena.dtype == torch.bfloat16:
+            return self._add_upload_bf16(items, weight, lossless, delta, base_arena, fused, dev)
         applies = re._lossy is None and not lossless and re.plan is not None
         if fused and not applies:
             raise _lib.CodecError("add_upload(fused=True) takes an Eden pipeline's lossy_compressed upload into a "
@@ -760,6 +775,27 @@ class WavgAccumulator:
                                                                   *re._fz.args, self.sums.data_ptr(), _stream(dev)))
             if re.single:
                 torch.index_select(self._scratch, 0, re._single_idx, out=self._row(c))
+            if c == 0 and re._gap_idx is not None:
+                self.sums.index_fill_(0, re._gap_idx, 0.0)
+        self.weights.append(weight)
+
+    def _add_upload_bf16(self, items, weight, lossless, delta, base16, fused, dev):
+        """add_upload against a bfloat16 base: every check, then RoundEnd._fold_eden_bf16."""
+        re = self.re
+        if re._lossy is not None or lossless or (fused is not None and not fused):
+            raise _lib.CodecError("add_upload with a bfloat16 base_arena takes an Eden pipeline's lossy_compressed "
+                                  "upload on the fused route only: ingest() into bfloat16 arenas is not offered")
+        items, bufs = re._ingest_begin(items, "eden", delta, base16, None, bf16=True)
+        re._raw16()   # its check, before anything is launched
+        w, c = self._next_weight(weight)
+        with torch.cuda.device(dev):
+            raw = re._fold_eden_bf16(items, bufs, base16 if delta else None, self.sums, w, c == 0)
+            if re.single:
+                at, row = re._raw16()["single_at"], self._row(c)
+                if delta:
+                    torch.add(base16.index_select(0, re._single_idx).float(), raw.index_select(0, at), out=row)
+                else:
+                    torch.index_select(raw, 0, at, out=row)
             if c == 0 and re._gap_idx is not None:
                 self.sums.index_fill_(0, re._gap_idx, 0.0)
         self.weights.append(weight)
@@ -899,6 +935,7 @@ class RoundEnd:
         self.pipeline = pipeline
         self._ingest_stage, self._ingest_done, self._ingest_tmp = {}, None, None
         self._single_idx = None   # accumulator(): the 1-element tensors' offsets on the device
+        self._raw16_tab = None    # _raw16(): the raw tensors' packed table (bfloat16 rounds)
 
     def _init_eden(self, tr, fused):
         """The Eden back end's plan and device tables (_device_seeds, _encode_apply)."""
@@ -994,7 +1031,7 @@ class RoundEnd:
             self._zero_gaps(out)
         return out
 
-    def _ingest_begin(self, items, kind, delta, base_arena, out):
+    def _ingest_begin(self, items, kind, delta, base_arena, out, bf16=False):
         """Every check ingest makes before it writes or launches anything ->
         (the items as a list, _ingest_check's payload arrays)."""
         items = list(items)
@@ -1005,7 +1042,7 @@ class RoundEnd:
             raise _lib.CodecError("ingest: delta=True needs base_arena")
         for a in (base_arena, out):
             if a is not None:
-                self._check_arena(a)
+                self._check_arena(a, bf16=bf16)
         return items, self._ingest_check(items, kind)
 
     def _ingest_check(self, items, kind):
@@ -1164,6 +1201,69 @@ class RoundEnd:
             _lib.check_agg(_lib.lib().ofl_apply_delta_ranges(base.data_ptr(), dst.data_ptr(), out.data_ptr(),
                                                              *self._rest.args, _stream(dev)))
 
+    def _raw16(self):
+        """The raw tensors (at most dim_threshold elements) as one packed
+        float32 buffer, for ofl_acc_side_ranges: tensor after tensor in slots
+        of 4 elements (the tensors' arena offsets are multiples of 64).  ->
+        {"raw", "table" (device int64 s | e | dst | cb), "nr", "slots", "at"
+        (tensor -> its first element in the buffer), "single_at" (device:
+        the 1-element tensors' places in it)}, made once."""
+        if self._raw16_tab is None:
+            raw = [i for i, n in enumerate(self.numels) if 0 < n <= self.dim_threshold]
+            if any(i not in set(raw) for i in self.single):
+                raise _lib.CodecError("bfloat16 arenas: 1-element tensors must be raw (dim_threshold >= 1)")
+            dst = np.cumsum([0] + [(self.numels[i] + 3) // 4 for i in raw]).astype(np.int64)
+            s = np.asarray([self.offsets[i] for i in raw], np.int64)
+            e = s + np.asarray([self.numels[i] for i in raw], np.int64)
+            at = {i: 4 * int(d) for i, d in zip(raw, dst)}
+            tab = np.concatenate([s, e, dst, 4 * dst[:-1]]).astype(np.int64)
+            self._raw16_tab = {
+                "raw": raw, "table": torch.from_numpy(tab).to(self.device), "nr": len(raw), "slots": int(dst[-1]),
+                "at": at, "single_at": torch.tensor([at[i] for i in self.single] or [0], dtype=torch.int64).to(self.device)}
+        return self._raw16_tab
+
+    def _fold_eden_bf16(self, items, bufs, base16, sums, w, first):
+        """EdenPipeline's payloads folded into the float64 sums against a
+        bfloat16 base (None: no base) without a float32 arena: one pinned
+        staging [raw tensors packed (_raw16) | planes | scales | seeds] and
+        one H2D; the big tensors by EdenPlan.decode_accumulate's bf16 route
+        (row pass and side arena), the raw ones by ofl_acc_side_ranges.  ->
+        the packed raw tensors on the device (float32)."""
+        dev, p, r16 = self.device, self.plan, self._raw16()
+        raw_bytes = (16 * r16["slots"] + 255) // 256 * 256
+        off_scales = raw_bytes + ((p.planes_bytes + 255) // 256 * 256 if p is not None else 0)
+        off_seeds = (off_scales + 4 * p.n_slices + 255) // 256 * 256 if p is not None else off_scales
+        nbytes = off_seeds + 4 * len(self.big)
+        st = self._ingest_staging("eden_bf16", [], nbytes)
+        host = st["host"][:max(nbytes, 1)]
+        hp = host.data_ptr()
+        raw = r16["raw"]
+        _copy_many([hp + 4 * r16["at"][i] for i in raw] + [hp + raw_bytes + p.planes_offsets[t] for t in range(len(self.big))],
+                   [bufs[i].ctypes.data for i in raw + self.big],
+                   [4 * self.numels[i] for i in raw] + (list(p.planes_nbytes) if p is not None else []))
+        if p is not None:
+            ha = host.numpy()
+            scales = ha[off_scales:off_scales + 4 * p.n_slices].view(np.float32)
+            seeds = ha[off_seeds:off_seeds + 4 * len(self.big)].view(np.uint32)
+            for t, i in enumerate(self.big):
+                m = dict(items[i][1][0]["int_to_float"])
+                fs = p.first_slice[t]
+                seeds[t] = int(m[0]) & 0xFFFFFFFF
+                scales[fs:fs + len(p.dims[t])] = [m[2 + 2 * k] for k in range(len(p.dims[t]))]
+        d = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        d.copy_(host, non_blocking=True)
+        self._ingest_sent()
+        raw_d = d[:raw_bytes].view(torch.float32)
+        if p is not None:
+            if self._codec_ws is None or self._codec_ws.numel() < p.ws_bytes:
+                self._codec_ws = torch.empty(max(p.ws_bytes, 256), dtype=torch.uint8, device=dev)
+            planes, seeds_d = d[raw_bytes:raw_bytes + max(p.planes_bytes, 1)], d[off_seeds:nbytes].view(torch.int32)
+            scales_d = d[off_scales:off_scales + 4 * p.n_slices].view(torch.float32)
+            p.decode_accumulate(planes, seeds_d, scales_d, sums, w, first, None, self._codec_ws, base=base16, bf16=True)
+        _lib.check(_lib.lib().ofl_acc_side_ranges(raw_d.data_ptr(), _ptr(base16), w, 1 if first else 0, sums.data_ptr(),
+                                                  r16["table"].data_ptr(), r16["nr"], r16["slots"], _stream(dev)))
+        return raw_d
+
     def _inflated(self):
         """The tensors whose payloads the lossy pipeline's backward inflates on
         the device (its host path takes the others: n < n_clusters, empty ones,
@@ -1247,7 +1347,15 @@ class RoundEnd:
         order from acc's table (ofl_wavg_delta_points), and the seeds come from
         the float64 average minus the base (ofl_agg_delta_seeds), the route the
         geometric median takes; never fused.  agg_out (float64, arena_numel
-        elements) receives the average; acc.sums holds it anyway.  An
+        elements) receives the average; acc.sums holds it anyway.
+        A bfloat16 base_arena (Eden pipelines) stands for its float32 widening:
+        the delta, seeds, draws, payloads and metadata are those of the float32
+        round on base_arena.float(), byte for byte (ofl_wavg_finish_bf16,
+        ofl_agg_delta_seeds_bf16), and the new model is that round's float32
+        model rounded once to nearest even, in a bfloat16 `out` (default: a
+        new one; may be base_arena): ofl_eden_decode_add_bf16 on the coded
+        tensors, ofl_apply_delta_ranges_bf16 on the raw ones.  `out` has the
+        base's dtype.  An
         accumulator is finished once.  All errors are raised before anything
         is launched or drawn from np.random.
         An AdaptiveAccumulator ("adam", "yogi", "adagrad"): one
@@ -1264,22 +1372,26 @@ class RoundEnd:
             raise _lib.CodecError("accumulator: finish() after finish()")
         if not acc.weights:
             raise _lib.CodecError("accumulator: finish() without an add()")
-        if base_arena is not None:
-            self._check_arena(base_arena)
+        bf16 = base_arena is not None and self._check_arena(base_arena, bf16=self._lossy is None)
+        if out is not None and self._check_arena(out, bf16=self._lossy is None) != bf16:
+            raise _lib.CodecError(f"finish(): out must have the base's dtype ({'bfloat16' if bf16 else 'float32'}), "
+                                  f"not {out.dtype}")
         if agg_out is not None and not (agg_out.dtype == torch.float64 and agg_out.numel() >= self.arena_numel):
             raise _lib.CodecError("agg_out must be float64 with arena_numel elements")
+        if bf16 and self.single:
+            self._raw16()   # its check, before anything is launched or drawn
         w64 = _f64_weights(acc.weights, len(acc.weights))
         wsum = self._wsum(w64)
         acc.finished = True
         L = _lib.lib()
         with torch.cuda.device(dev):
             delta = self._empty_arena()
-            _lib.check_agg(L.ofl_wavg_finish(acc.sums.data_ptr(), wsum, _ptr(base_arena), self.arena_numel, None,
-                                             delta.data_ptr(), _stream(dev)))
+            _lib.check_agg((L.ofl_wavg_finish_bf16 if bf16 else L.ofl_wavg_finish)(
+                acc.sums.data_ptr(), wsum, _ptr(base_arena), self.arena_numel, None, delta.data_ptr(), _stream(dev)))
             if self.single:
                 ns, C = len(self.single), len(w64)
                 rows = [acc._table[c] for c in range(C)]
-                b1 = base_arena.index_select(0, self._single_idx) if base_arena is not None else None
+                b1 = base_arena.index_select(0, self._single_idx).float() if base_arena is not None else None
                 a1 = torch.empty(ns, dtype=torch.float64, device=dev)
                 d1 = torch.empty(ns, dtype=torch.float32, device=dev)
                 _points_launch(rows, w64, wsum, b1, np.arange(ns), a1, d1, dev, self._ws)
@@ -1382,9 +1494,20 @@ class RoundEnd:
         if self._gap_idx is not None:
             out.index_fill_(0, self._gap_idx, 0.0)
 
-    def _check_arena(self, x):
-        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= self.arena_numel):
-            raise _lib.CodecError("arenas must be contiguous float32 device tensors of arena_numel elements")
+    def _check_arena(self, x, bf16=False):
+        """Every arena argument's check -> True for a bfloat16 arena, which
+        only the calls that pass bf16=True take (the weighted average's
+        streaming round with an Eden pipeline); the error names the dtype found."""
+        ok = (torch.float32, torch.bfloat16) if bf16 else (torch.float32,)
+        if not (x.is_cuda and x.dtype in ok and x.is_contiguous() and x.numel() >= self.arena_numel):
+            only = ""
+            if x.dtype == torch.bfloat16:
+                only = ("; bfloat16 arenas are taken by the weighted average's accumulator() with an Eden pipeline "
+                        "only -- add(), add_upload(base_arena=) and finish(): run(), ingest(), the medians, the "
+                        "adaptive optimisers and the KC / SKC / STC pipelines are float32 only (float16: nowhere)")
+            raise _lib.CodecError(f"arenas must be contiguous {' or '.join(str(t)[6:] for t in ok)} device tensors of "
+                                  f"arena_numel elements, not {str(x.dtype)[6:]}{only}")
+        return x.dtype == torch.bfloat16
 
     def _empty_arena(self):
         return torch.empty(self.arena_numel, dtype=torch.float32, device=self.device)
@@ -1465,6 +1588,10 @@ class RoundEnd:
         out = self._seeds.data_ptr(), self._seed_sums.data_ptr(), self._packed.data_ptr(), _stream(self.device)
         if isinstance(src, _AggSeeds):
             dp = self._stage_args([draws])
+            if src.base is not None and src.base.dtype == torch.bfloat16:   # finish() on a bfloat16 base: float64 sums
+                _lib.check_agg(L.ofl_agg_delta_seeds_bf16(src.agg.data_ptr(), src.base.data_ptr(), *self._seed.args, dp,
+                                                          *out))
+                return None
             _lib.check_agg(L.ofl_agg_delta_seeds(src.agg.data_ptr(), src.is_f64, _ptr(src.base), *self._seed.args, dp,
                                                  *out))
             return None
@@ -1492,8 +1619,12 @@ class RoundEnd:
     def _encode_apply(self, delta, base_arena, payloads, out, wavg):
         """run() from the seeds on: encode, payloads, decode fused with
         apply_delta, the small tensors' float32 payloads and the gap zeroing.
-        wavg: (device args, collaborators, weight sum) for the fused encode."""
+        wavg: (device args, collaborators, weight sum) for the fused encode.
+        A bfloat16 base_arena (finish()): the float32 delta is encoded as it
+        is, and decode and apply round the float32 model once into a
+        bfloat16 out."""
         dev = self.device
+        bf16 = base_arena is not None and base_arena.dtype == torch.bfloat16
         L = _lib.lib()
         T = len(self.numels)
         fused = wavg is not None
@@ -1504,7 +1635,7 @@ class RoundEnd:
             # 3. encode, (payloads), decode in place, apply
             result = [None] * len(self.numels) if payloads else None
             if out is None:
-                out = self._empty_arena()
+                out = torch.empty_like(base_arena[:self.arena_numel]) if bf16 else self._empty_arena()
             if self.plan is not None:
                 p = self.plan
                 sd = self._seeds.index_select(0, self._big_idx)
@@ -1541,7 +1672,10 @@ class RoundEnd:
                     for i in small:
                         result[i] = (hostmem.bytes_from(dh.ctypes.data + 4 * o, 4 * self.numels[i]), [{"int_list": list(self.shapes[i])}])
                         o += self.numels[i]
-            if base_arena is not None:
+            if bf16:   # without a plan every tensor is in _rest
+                _lib.check_agg(L.ofl_apply_delta_ranges_bf16(base_arena.data_ptr(), delta.data_ptr(), out.data_ptr(),
+                                                             *self._rest.args, _stream(dev)))
+            elif base_arena is not None:
                 if self.plan is not None:
                     _lib.check_agg(L.ofl_apply_delta_ranges(base_arena.data_ptr(), delta.data_ptr(), out.data_ptr(),
                                                             *self._rest.args, _stream(dev)))

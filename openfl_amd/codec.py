@@ -193,22 +193,38 @@ class EdenPlan:
                                                y_arena.data_ptr(), ws.data_ptr() if ws is not None else None,
                                                ws.numel() if ws is not None else 0, st.cuda_stream))
 
-    def decode_accumulate(self, planes, seeds, scales, sums, weight, first, y_small, ws, stream=None, base=None):
+    def decode_accumulate(self, planes, seeds, scales, sums, weight, first, y_small, ws, stream=None, base=None,
+                          bf16=False):
         """decode (+ base) folded into the streaming average's float64 sums
         (ofl_eden_decode_accumulate): on the slices above 2^15 elements
         sums = f64(y) * weight when first, else sums + f64(y) * weight, for
         the y that decode(..., base=base) would write, which is not written.
         sums: float64[arena_numel]; y_small: float32[arena_numel], written
         with decode's y on the slices of at most 2^15 elements only (for
-        ofl_wavg_accumulate_ranges); None is allowed when the plan has none."""
+        ofl_wavg_accumulate_ranges); None is allowed when the plan has none.
+        A bfloat16 base (or bf16=True, for an upload without a base) takes
+        ofl_eden_decode_accumulate_bf16: the sums on every slice, the small
+        ones included, are those of base.float(), bit for bit; the small
+        slices go through the plan's side arena (_side_arena) and are folded
+        by the call itself, so y_small is not used and may be None."""
         self._check(sums, torch.float64, self.arena_numel)
         self._check(planes, torch.uint8, self.planes_bytes)
         self._check(scales, torch.float32, self.n_slices)
         self._check(seeds, torch.int32, len(self.numels))
+        st = stream if stream is not None else torch.cuda.current_stream(sums.device)
+        if bf16 or (base is not None and base.dtype == torch.bfloat16):
+            if base is not None:
+                self._check(base, torch.bfloat16, self.arena_numel)
+            side = self._side_arena(sums.device, st)
+            _lib.check(self._L.ofl_eden_decode_accumulate_bf16(
+                self._h, planes.data_ptr(), seeds.data_ptr(), scales.data_ptr(),
+                base.data_ptr() if base is not None else None, float(weight), 1 if first else 0, sums.data_ptr(),
+                side.data_ptr() if side is not None else None, ws.data_ptr() if ws is not None else None,
+                ws.numel() if ws is not None else 0, st.cuda_stream))
+            return
         for a in (y_small, base):
             if a is not None:
                 self._check(a, torch.float32, self.arena_numel)
-        st = stream if stream is not None else torch.cuda.current_stream(sums.device)
         _lib.check(self._L.ofl_eden_decode_accumulate(self._h, planes.data_ptr(), seeds.data_ptr(), scales.data_ptr(),
                                                       base.data_ptr() if base is not None else None, float(weight),
                                                       1 if first else 0, sums.data_ptr(),
@@ -216,9 +232,11 @@ class EdenPlan:
                                                       ws.data_ptr() if ws is not None else None,
                                                       ws.numel() if ws is not None else 0, st.cuda_stream))
 
-    def accumulate_launches(self):
-        """The launches of a decode_accumulate, as launches() reports them."""
-        return self._launches(3)
+    def accumulate_launches(self, bf16=False):
+        """The launches of a decode_accumulate, as launches() reports them;
+        bf16=True: against a bfloat16 base (the side arena's fold, which is
+        not the plan's, is not listed)."""
+        return self._launches(6 if bf16 else 3)
 
     def roundtrip(self, x_arena, seeds, y_arena, scales, ws, stream=None, base=None):
         """y_arena = decode(encode(x_arena)) (+ base when given) and the
@@ -278,8 +296,9 @@ class EdenPlan:
     def profile_collect(self, encode):
         """-> (per-launch summed ms, number of recorded calls).  encode: False
         / True, 2 for the round trip's launches, 3 for decode_accumulate's,
-        4 / 5 for encode's / decode's with bfloat16 arenas."""
-        which = int(encode) if encode in (2, 3, 4, 5) else 1 if encode else 0
+        4 / 5 for encode's / decode's with bfloat16 arenas, 6 for
+        decode_accumulate's against a bfloat16 base."""
+        which = int(encode) if encode in (2, 3, 4, 5, 6) else 1 if encode else 0
         n = self._L.ofl_eden_plan_num_launches(self._h, which)
         ms = np.zeros(max(n, 1), np.float64)
         calls = ctypes.c_int()

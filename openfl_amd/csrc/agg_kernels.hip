@@ -30,6 +30,7 @@
 
 #include "median_net.h"
 #include "ofl_codec.h"
+#include "ofl_util.h"
 
 namespace agg {
 
@@ -1482,6 +1483,192 @@ int ofl_adaptive_finish(const float* g, const float* base, int64_t n, float* p, 
     const int vec = aligned16(&g, 1, base, p, a.io.m, v, agg_out, delta_out);
     hipLaunchKernelGGL(agg::k_adaptive_finish, dim3(grid_for(n, 4)), dim3(agg::kNT), 0,
                        static_cast<hipStream_t>(stream), a, vec);
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+}  // extern "C"
+
+// ---- the weighted average's streaming round on bfloat16 model arenas ------------
+// A bf16 arena (uint16_t) stands for its exact float32 widening: each kernel is
+// its float32 form above with widen(x16[i]) where that reads x[i], the same
+// operations in the same order, contraction off where that has it off.  Only
+// the new model is rounded, once, to nearest even (k_apply_ranges_bf16; the
+// coded tensors by ofl_eden_decode_add_bf16).  A quad of a bf16 arena is one
+// 8-byte access where every arena of the launch is aligned for its 4-element
+// access (vec); widen / round: ofl_util.h.
+
+namespace agg {
+
+using ofl::bf16_hi;
+using ofl::bf16_lo;
+using ofl::bf16_rne;
+
+// k_wavg_accumulate from a bf16 arena: reads 2 + 8, writes 8 bytes per element
+struct Acc16Args {
+    const uint16_t* x16;
+    double w;
+    int first;
+    double* sums;
+    int64_t n;
+};
+__global__ __launch_bounds__(kNT) void k_wavg_accumulate_bf16(Acc16Args a, int vec) {
+    quads_then_tail(a.n, vec,
+        [&](int64_t i) {
+#pragma clang fp contract(off)
+            const uint2 v = *reinterpret_cast<const uint2*>(a.x16 + i);
+            double2* s2 = reinterpret_cast<double2*>(a.sums + i);
+            double2 lo, hi;
+            lo.x = (double)bf16_lo(v.x) * a.w; lo.y = (double)bf16_hi(v.x) * a.w;
+            hi.x = (double)bf16_lo(v.y) * a.w; hi.y = (double)bf16_hi(v.y) * a.w;
+            if (!a.first) {
+                const double2 p = s2[0], q = s2[1];
+                lo.x = p.x + lo.x; lo.y = p.y + lo.y;
+                hi.x = q.x + hi.x; hi.y = q.y + hi.y;
+            }
+            s2[0] = lo;
+            s2[1] = hi;
+        },
+        [&](int64_t i) {
+#pragma clang fp contract(off)
+            const double p = (double)bf16_lo(a.x16[i]) * a.w;
+            a.sums[i] = a.first ? p : a.sums[i] + p;
+        });
+}
+
+// k_wavg_finish against a bf16 base: reads 8 + 2, writes 8 + 4 (+ 8 with delta64)
+struct Finish16Args {
+    double wsum;
+    const uint16_t* base16;  // nullable: delta = average when absent
+    double* sums;            // divided in place
+    double* delta64;         // nullable
+    float* delta32;          // nullable
+    int64_t n;
+};
+__global__ __launch_bounds__(kNT) void k_wavg_finish_bf16(Finish16Args a, int vec) {
+    quads_then_tail(a.n, vec,
+        [&](int64_t i) {
+#pragma clang fp contract(off)
+            double2* s2 = reinterpret_cast<double2*>(a.sums + i);
+            double2 lo = s2[0], hi = s2[1];
+            lo.x = lo.x / a.wsum; lo.y = lo.y / a.wsum;
+            hi.x = hi.x / a.wsum; hi.y = hi.y / a.wsum;
+            s2[0] = lo;
+            s2[1] = hi;
+            if (!a.delta64 && !a.delta32) return;
+            if (a.base16) {
+                const uint2 b = *reinterpret_cast<const uint2*>(a.base16 + i);
+                lo.x = lo.x - (double)bf16_lo(b.x); lo.y = lo.y - (double)bf16_hi(b.x);
+                hi.x = hi.x - (double)bf16_lo(b.y); hi.y = hi.y - (double)bf16_hi(b.y);
+            }
+            if (a.delta64) {
+                double2* d2 = reinterpret_cast<double2*>(a.delta64 + i);
+                d2[0] = lo;
+                d2[1] = hi;
+            }
+            if (a.delta32)
+                *reinterpret_cast<float4*>(a.delta32 + i) = make_float4((float)lo.x, (float)lo.y, (float)hi.x, (float)hi.y);
+        },
+        [&](int64_t i) {
+#pragma clang fp contract(off)
+            const double avg = a.sums[i] / a.wsum;
+            const double d = a.base16 ? avg - (double)bf16_lo(a.base16[i]) : avg;
+            a.sums[i] = avg;
+            if (a.delta64) a.delta64[i] = d;
+            if (a.delta32) a.delta32[i] = (float)d;
+        });
+}
+
+// k_agg_ranges<double> against a bf16 base
+__global__ __launch_bounds__(kNT) void k_agg_ranges_bf16(const double* agg, const uint16_t* base16, Ranges rg, double* out) {
+#pragma clang fp contract(off)
+    const int64_t total = rg.total();
+    for (int64_t j = (int64_t)blockIdx.x * kNT + threadIdx.x; j < total; j += (int64_t)gridDim.x * kNT) {
+        int64_t i;
+        rg.find(j, i);
+        out[j] = base16 ? agg[i] - (double)bf16_lo(base16[i]) : agg[i];
+    }
+}
+
+// k_apply_ranges on a bf16 model: out16 = bf16(widen(base16) + delta32), the one
+// rounding of the round.  A lane reads its element before it writes it, so
+// out16 may be base16.  The packed index runs in steps of 4: where the four
+// lie in one range at an arena index that is a multiple of 4 they are one
+// 16-byte delta load and 8-byte base load and store.
+__global__ __launch_bounds__(kNT) void k_apply_ranges_bf16(const uint16_t* base16, const float* delta, uint16_t* out16,
+                                                           Ranges rg, int vec) {
+#pragma clang fp contract(off)
+    const int64_t total = rg.total();
+    for (int64_t j = 4 * ((int64_t)blockIdx.x * kNT + threadIdx.x); j < total; j += 4 * (int64_t)gridDim.x * kNT) {
+        int64_t i;
+        const int r = rg.find(j, i);
+        if (vec && (i & 3) == 0 && j + 4 <= rg.dst[r + 1]) {
+            const uint2 b = *reinterpret_cast<const uint2*>(base16 + i);
+            const float4 d = *reinterpret_cast<const float4*>(delta + i);
+            *reinterpret_cast<uint2*>(out16 + i) = make_uint2(ofl::bf16_pack(bf16_lo(b.x) + d.x, bf16_hi(b.x) + d.y),
+                                                              ofl::bf16_pack(bf16_lo(b.y) + d.z, bf16_hi(b.y) + d.w));
+        } else {
+            for (int64_t q = j; q < j + 4 && q < total; ++q) {
+                rg.find(q, i);
+                out16[i] = (uint16_t)bf16_rne(__float_as_uint(bf16_lo(base16[i]) + delta[i]));
+            }
+        }
+    }
+}
+
+}  // namespace agg
+
+extern "C" {
+
+int ofl_wavg_accumulate_bf16(const uint16_t* x16, double w, int first, int64_t n, double* sums, void* stream) {
+    if (n < 0 || (n && (!x16 || !sums))) return afail(OFL_EINVAL, "wavg_accumulate_bf16: bad arguments");
+    if (n == 0) return OFL_OK;
+    const agg::Acc16Args a{x16, w, first ? 1 : 0, sums, n};
+    const int vec = (reinterpret_cast<uintptr_t>(x16) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sums) & 15u) == 0;
+    hipLaunchKernelGGL(agg::k_wavg_accumulate_bf16, dim3(grid_for(n, 4)), dim3(agg::kNT), 0,
+                       static_cast<hipStream_t>(stream), a, vec);
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_wavg_finish_bf16(double* sums, double wsum, const uint16_t* base16, int64_t n, double* delta64_out,
+                         float* delta32_out, void* stream) {
+    if (n < 0 || (n && !sums)) return afail(OFL_EINVAL, "wavg_finish_bf16: bad arguments");
+    if (delta64_out && delta64_out == sums) return afail(OFL_EINVAL, "wavg_finish_bf16: delta64_out must not be the sums");
+    if (n == 0) return OFL_OK;
+    const agg::Finish16Args a{wsum, base16, sums, delta64_out, delta32_out, n};
+    const float* const* none = nullptr;
+    const int vec = (reinterpret_cast<uintptr_t>(base16) & 7u) == 0 && aligned16(none, 0, sums, delta64_out, delta32_out);
+    hipLaunchKernelGGL(agg::k_wavg_finish_bf16, dim3(grid_for(n, 4)), dim3(agg::kNT), 0,
+                       static_cast<hipStream_t>(stream), a, vec);
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_agg_delta_seeds_bf16(const double* agg_dev, const uint16_t* base16, int nranges, const int64_t* starts_dev,
+                             const int64_t* dst_dev, int64_t total, const int64_t* draws_dev, uint32_t* seeds_dev,
+                             double* sums_dev, double* packed_dev, void* stream) {
+    if (nranges < 1 || total < 0) return afail(OFL_EINVAL, "agg seeds: bad sizes");
+    if (!agg_dev || !starts_dev || !dst_dev || !draws_dev || !seeds_dev || !sums_dev || (total > 0 && !packed_dev))
+        return afail(OFL_EINVAL, "agg seeds: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const agg::Ranges rg{starts_dev, dst_dev, nranges};
+    if (total > 0)
+        hipLaunchKernelGGL(agg::k_agg_ranges_bf16, dim3(grid_for(total, 1)), dim3(agg::kNT), 0, st, agg_dev, base16, rg,
+                           packed_dev);
+    launch_sums_seeds<double>(packed_dev, dst_dev, nranges, draws_dev, seeds_dev, sums_dev, st);
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_apply_delta_ranges_bf16(const uint16_t* base16, const float* delta32, uint16_t* out16, int nranges,
+                                const int64_t* starts, const int64_t* dst, int64_t total, void* stream) {
+    if (nranges < 1 || total <= 0) return OFL_OK;
+    if (!base16 || !delta32 || !out16 || !starts || !dst) return afail(OFL_EINVAL, "apply_delta_ranges_bf16: bad arguments");
+    const int vec = ((reinterpret_cast<uintptr_t>(base16) | reinterpret_cast<uintptr_t>(out16)) & 7u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(delta32) & 15u) == 0;
+    hipLaunchKernelGGL(agg::k_apply_ranges_bf16, dim3(grid_for(total, 4)), dim3(agg::kNT), 0,
+                       static_cast<hipStream_t>(stream), base16, delta32, out16, agg::Ranges{starts, dst, nranges}, vec);
     AHIP(hipGetLastError());
     return OFL_OK;
 }

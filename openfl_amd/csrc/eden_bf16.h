@@ -38,17 +38,7 @@
 
 __device__ void raw_store_i32x2(i32x2 v, rsrc_t r, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.store.v2i32");
 
-// float32 bits -> bf16 bits, round to nearest even: the carry of the rounding
-// runs into the exponent (0x7f7fffff -> +inf), +-0, +-inf and denormals follow
-// by the same rule; a NaN keeps its sign and stays one (the quiet bit is set:
-// its top 7 mantissa bits may all be 0)
-DEVI uint32_t bf16_rne(uint32_t u) {
-    const uint32_t r = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    return (u & 0x7fffffffu) > 0x7f800000u ? (u >> 16) | 0x40u : r;
-}
-DEVI float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }          // the element at the lower address
-DEVI float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-DEVI uint32_t bf16_pack(float lo, float hi) { return bf16_rne(__float_as_uint(lo)) | (bf16_rne(__float_as_uint(hi)) << 16); }
+// bf16_rne, bf16_lo, bf16_hi, bf16_pack: ofl_util.h (shared with agg_kernels.hip)
 DEVI float bf16_out(const uint16_t* b, int64_t i, float v) {  // element i of y before its rounding
     return b ? add_rn(bf16_lo(b[i]), v) : v;
 }

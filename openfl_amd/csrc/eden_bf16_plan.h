@@ -47,6 +47,14 @@ inline const char* bf16_resolve(const Plan& pl, const Launch& l, bool enc, int n
     return nullptr;
 }
 
+// decode-accumulate against a bf16 base (ofl_eden_decode_accumulate_bf16,
+// eden_dec_acc_bf16.h): acc_resolve's launches with the accumulate kernels'
+// bf16 variants, one entry per AccKernelId
+constexpr const char* kAcc16KernelName[ACC_KERNEL_COUNT] = {"ofl::k_dec_acc_rowC_bf16", "ofl::k_dec_acc_rowC2_bf16"};
+// the bytes such a row launch moves, from its decode launch's: per valid
+// element base 2 + sums 8 + 8 in place of y 4 (acc_bytes_moved with a 2-byte base)
+inline int64_t acc16_bytes_moved(const Launch& l) { return l.bytes_moved + 4 * l.bytes_alg - l.bytes_alg / 2; }
+
 // The bytes of a bf16 row launch, from its float32 launch's: the launch's
 // algorithmic bytes are the arena's (x read, or y written), 4 per valid
 // element there and 2 here; the intermediate as before.  (A base adds 4 / 2

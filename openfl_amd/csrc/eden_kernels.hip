@@ -2340,6 +2340,8 @@ __global__ __launch_bounds__(256) void k_finalize(KArgs a) {
 #include "eden_dec_acc.h"
 // the row passes' bf16 arena I/O and the small slices' widen / narrow, after it
 #include "eden_bf16.h"
+// decode's last row pass into the sums against a bf16 base and the side arena's fold, after it
+#include "eden_dec_acc_bf16.h"
 
 }  // namespace ofl
 
@@ -2366,7 +2368,7 @@ struct ofl_eden_plan {
     const char* rt_err = nullptr;  // why the plan has none (ofl_eden_roundtrip reports it)
     // profiling: events around every launch of every call while enabled
     bool prof = false;
-    std::vector<std::vector<hipEvent_t>> prof_ev[6];  // [dec, enc, round trip, decode-accumulate, bf16 enc, bf16 dec][call][launch+1]
+    std::vector<std::vector<hipEvent_t>> prof_ev[7];  // [dec, enc, round trip, decode-accumulate, bf16 enc, bf16 dec, bf16 decode-accumulate][call][launch+1]
     std::vector<hipEvent_t> ev_pool;
     ofl::SliceDesc* d_slices = nullptr;
     ofl::SliceDesc* d_rt_slices = nullptr;  // rt.slices
@@ -2473,11 +2475,18 @@ constexpr KernelEntry kBf16Kernels[eden::BF16_KERNEL_COUNT] = {
     {eden::KERNEL_COUNT, ofl::k_dec_rowC2_bf16, ofl::kRowNT, ofl::kRow2Smem},
 };
 
+// decode-accumulate's kernels against a bf16 base, one entry per eden::AccKernelId
+constexpr KernelEntry kAcc16Kernels[eden::ACC_KERNEL_COUNT] = {
+    {eden::KERNEL_COUNT, ofl::k_dec_acc_rowC_bf16, ofl::kRowNT, ofl::kRowSmemA},
+    {eden::KERNEL_COUNT, ofl::k_dec_acc_rowC2_bf16, ofl::kRowNT, ofl::kRow2Smem},
+};
+
 hipError_t set_all_attrs() {
     const std::pair<const KernelEntry*, int> tabs[] = {{kKernels, (int)eden::KERNEL_COUNT},
                                                        {kRtKernels, (int)eden::RT_KERNEL_COUNT},
                                                        {kAccKernels, (int)eden::ACC_KERNEL_COUNT},
-                                                       {kBf16Kernels, (int)eden::BF16_KERNEL_COUNT}};
+                                                       {kBf16Kernels, (int)eden::BF16_KERNEL_COUNT},
+                                                       {kAcc16Kernels, (int)eden::ACC_KERNEL_COUNT}};
     for (const auto& [tab, n] : tabs)
         for (int i = 0; i < n; ++i) {
             const KernelEntry& k = tab[i];
@@ -2489,7 +2498,7 @@ hipError_t set_all_attrs() {
 }
 
 // which of a plan's launch lists a call runs (the ABI's `encode` argument)
-enum { RUN_DEC = 0, RUN_ENC = 1, RUN_RT = 2, RUN_ACC = 3, RUN_ENC16 = 4, RUN_DEC16 = 5, RUN_COUNT };
+enum { RUN_DEC = 0, RUN_ENC = 1, RUN_RT = 2, RUN_ACC = 3, RUN_ENC16 = 4, RUN_DEC16 = 5, RUN_ACC16 = 6, RUN_COUNT };
 int num_launches(const ofl_eden_plan* pl, int which) {
     const bool enc = which == RUN_ENC || which == RUN_ENC16;
     return (int)(which == RUN_RT ? pl->rt.list.size() : enc ? pl->p.enc.size() : pl->p.dec.size());
@@ -2503,6 +2512,7 @@ struct Picked {
     const KernelEntry* k;
     const char* name;
     bool acc;  // a decode-accumulate row launch (its bytes: eden::acc_bytes_moved)
+    bool acc16;  // the same against a bf16 base (eden::acc16_bytes_moved)
     bool bf;   // a row launch on a bf16 arena (its bytes: eden::bf16_bytes_moved / _alg)
 };
 const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, bool wavg, bool planes8, Picked& p) {
@@ -2517,7 +2527,7 @@ const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, boo
         err = eden::rt_resolve(pl->p, pl->rt.list[idx], ncu, wavg, x);
         p.r = x.r;
         if (x.rt) rt = eden::RT_ROW;
-    } else if (which == RUN_ACC) {
+    } else if (which == RUN_ACC || which == RUN_ACC16) {
         p.l = &pl->p.dec[idx];
         err = eden::acc_resolve(pl->p, *p.l, ncu, planes8, p.r, acc);
     } else {
@@ -2525,10 +2535,12 @@ const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, boo
         err = eden::resolve(pl->p, *p.l, which == RUN_ENC, ncu, wavg, planes8, p.r);
     }
     if (err) return err;
-    p.acc = acc >= 0;
+    p.acc16 = acc >= 0 && which == RUN_ACC16;
+    p.acc = acc >= 0 && !p.acc16;
     p.bf = bf >= 0;
-    p.k = rt >= 0 ? &kRtKernels[rt] : acc >= 0 ? &kAccKernels[acc] : bf >= 0 ? &kBf16Kernels[bf] : &kKernels[p.r.id];
-    p.name = rt >= 0 ? eden::kRtKernelName[rt] : acc >= 0 ? eden::kAccKernelName[acc]
+    p.k = rt >= 0 ? &kRtKernels[rt] : p.acc16 ? &kAcc16Kernels[acc] : acc >= 0 ? &kAccKernels[acc]
+          : bf >= 0 ? &kBf16Kernels[bf] : &kKernels[p.r.id];
+    p.name = rt >= 0 ? eden::kRtKernelName[rt] : p.acc16 ? eden::kAcc16KernelName[acc] : acc >= 0 ? eden::kAccKernelName[acc]
              : bf >= 0 ? eden::kBf16KernelName[bf] : eden::kKernelName[p.r.id];
     return nullptr;
 }
@@ -2999,6 +3011,54 @@ int ofl_eden_decode_add_bf16(ofl_eden_plan_t pl, const uint8_t* planes_arena, co
     return OFL_OK;
 }
 
+// the checks and the launch of a k_acc_side_ranges over `slots` slots of a
+// QRanges table on the device
+static int acc_side_launch(const char* what, const float* side, const uint16_t* base16, double w, int first, double* sums,
+                           const int64_t* tab_dev, int nr, int64_t slots, hipStream_t st) {
+    if (nr < 1 || slots <= 0) return OFL_OK;
+    if (!side || !sums || !tab_dev) return fail(OFL_EINVAL, std::string(what) + ": null argument");
+    if ((reinterpret_cast<uintptr_t>(base16) & 1u) || (reinterpret_cast<uintptr_t>(side) & 3u) ||
+        (reinterpret_cast<uintptr_t>(sums) & 7u))
+        return fail(OFL_EINVAL, std::string(what) + ": misaligned argument");
+    // whole slots take the 16- and 8-byte accesses only where all three are aligned for them
+    const int vec = ((reinterpret_cast<uintptr_t>(side) | reinterpret_cast<uintptr_t>(sums)) & 15u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(base16) & 7u) == 0;
+    hipLaunchKernelGGL(ofl::k_acc_side_ranges, dim3(range_grid(slots)), dim3(ofl::kRangeNT), 0, st,
+                       ofl::AccSideArgs{side, base16, sums, w, first ? 1 : 0}, ofl::QRanges{tab_dev, nr}, vec);
+    HIP_TRY(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_acc_side_ranges(const float* side, const uint16_t* base16, double w, int first, double* sums,
+                        const int64_t* table_dev, int nranges, int64_t slots, void* stream) {
+    return acc_side_launch("acc_side_ranges", side, base16, w, first, sums, table_dev, nranges, slots,
+                           static_cast<hipStream_t>(stream));
+}
+
+int ofl_eden_decode_accumulate_bf16(ofl_eden_plan_t pl, const uint8_t* planes_arena, const uint32_t* seeds,
+                                    const float* scales, const uint16_t* base16, double w, int first, double* sums,
+                                    float* y_side, void* ws, size_t ws_bytes, void* stream) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    if (!planes_arena || !seeds || !scales || !sums) return fail(OFL_EINVAL, "decode_accumulate_bf16: null argument");
+    if (reinterpret_cast<uintptr_t>(sums) & 15u) return fail(OFL_EINVAL, "decode_accumulate_bf16: the sums must be 16-byte aligned");
+    if (int rc = prep_bf16(pl, "decode_accumulate_bf16", nullptr, base16, y_side)) return rc;
+    ofl::KArgs a;
+    if (int rc = prep_args(pl, a, ws, ws_bytes)) return rc;
+    a.pin = planes_arena;
+    a.d = pl->d_slices16;  // the tiny / small slices in the side arena
+    a.xout = y_side;       // their decode kernels alone write it: decoded, no base (yadd stays null)
+    a.sums = sums;
+    a.base16 = base16;
+    a.seeds = seeds;
+    a.scales_in = scales;
+    a.acc_w = w;
+    a.acc_first = first ? 1 : 0;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = run(pl, RUN_ACC16, a, st)) return rc;
+    const eden::SmallRanges& R = pl->rg16[1];
+    return acc_side_launch("decode_accumulate_bf16", y_side, base16, w, first, sums, pl->d_rg16[1], R.nr, R.slots, st);
+}
+
 int64_t ofl_eden_roundtrip_workspace_bytes(ofl_eden_plan_t pl) {
     return pl && !pl->rt_err ? eden::rt_workspace_bytes(pl->p, pl->rt) : -1;
 }
@@ -3293,8 +3353,10 @@ int ofl_eden_plan_launch_info(ofl_eden_plan_t pl, int encode, int idx, char* nam
     if (int rc = resolve_plain(pl, encode, idx, p)) return rc;
     if (name && cap > 0) snprintf(name, (size_t)cap, "%s", p.name);
     if (blocks) *blocks = p.l->blocks;
-    if (bytes_moved) *bytes_moved = p.acc ? eden::acc_bytes_moved(*p.l) : p.bf ? eden::bf16_bytes_moved(*p.l) : p.l->bytes_moved;
-    if (bytes_alg) *bytes_alg = p.acc ? 0 : p.bf ? eden::bf16_bytes_alg(*p.l) : p.l->bytes_alg;
+    if (bytes_moved)
+        *bytes_moved = p.acc16 ? eden::acc16_bytes_moved(*p.l) : p.acc ? eden::acc_bytes_moved(*p.l)
+                       : p.bf ? eden::bf16_bytes_moved(*p.l) : p.l->bytes_moved;
+    if (bytes_alg) *bytes_alg = p.acc || p.acc16 ? 0 : p.bf ? eden::bf16_bytes_alg(*p.l) : p.l->bytes_alg;
     return OFL_OK;
 }
 

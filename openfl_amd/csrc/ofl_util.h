@@ -1,4 +1,5 @@
-// ofl_util.h -- small host-side helpers shared by the kernel sources.
+// ofl_util.h -- small helpers shared by the kernel sources: host-side ones, and
+// the device's bfloat16 widen / round.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,6 +39,26 @@ struct ScopeExit {
 };
 
 }  // namespace ofl_util
+
+#if defined(__HIPCC__)  // device code: the .hip sources
+namespace ofl {
+// bfloat16 <-> float32 on the device, one copy for every kernel source.
+// float32 bits -> bf16 bits, round to nearest even: the carry of the rounding
+// runs into the exponent (0x7f7fffff -> +inf), +-0, +-inf and denormals follow
+// by the same rule; a NaN keeps its sign and stays one (the quiet bit is set:
+// its top 7 mantissa bits may all be 0)
+__device__ __forceinline__ uint32_t bf16_rne(uint32_t u) {
+    const uint32_t r = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    return (u & 0x7fffffffu) > 0x7f800000u ? (u >> 16) | 0x40u : r;
+}
+// a 32-bit word holds two bf16 elements; widening is exact
+__device__ __forceinline__ float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }  // the element at the lower address
+__device__ __forceinline__ float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+__device__ __forceinline__ uint32_t bf16_pack(float lo, float hi) {
+    return bf16_rne(__float_as_uint(lo)) | (bf16_rne(__float_as_uint(hi)) << 16);
+}
+}  // namespace ofl
+#endif
 
 namespace ofl {
 // f(0..n-1) on the caller and at least `workers` threads of a persistent

@@ -26,6 +26,10 @@ One process, windows alternated (A B A B A B, the minimum and the spread of each
   --upload-stream   instead: the round end from Eden-coded uploads, add_upload x
               C + finish, the decode fused with the accumulate against ingest +
               add, and the last row passes alone (upload_stream).
+  --upload-stream --bf16   instead: that round with a bfloat16 base and model
+              against the float32 round on the widened base, same plans, and
+              k_dec_acc_rowC2_bf16 / ofl_wavg_finish_bf16 beside their float32
+              forms (upload_stream_bf16).
 Prints one JSON line.
 """
 import argparse
@@ -348,6 +352,106 @@ def upload_stream(args):
           flush=True)
 
 
+def upload_stream_bf16(args):
+    """--upload-stream --bf16: add_upload x C + finish with a bfloat16 base and a
+    bfloat16 new model against the fused float32 round on the widened base --
+    the same RoundEnd, plans, uploads and weights -- in alternated windows of
+    one process; then the kernels that differ, alone: the last row passes
+    under the plan's launch events (k_dec_acc_rowC / rowC2 against their _bf16
+    forms: base 4 -> 2 B per element) and ofl_wavg_finish against
+    ofl_wavg_finish_bf16 under device events (24 -> 22 B per element)."""
+    import torch
+    from openfl_amd import _lib
+    from openfl_amd import aggregation as A
+    from openfl_amd.pipelines import EdenPipeline
+    from openfl_amd.workloads import WORKLOADS
+    dev = torch.device("cuda", 0)
+    shapes = [tuple(s) for _, s in WORKLOADS[args.workload]()]
+    pipe = EdenPipeline(n_bits=8, device=dev, seed_mode="fast")
+    re = A.RoundEnd(pipe, shapes, dev)
+    C, n = args.collaborators, re.arena_numel
+    g = torch.Generator(device=dev)
+    arenas = []
+    for c in range(C + 1):
+        g.manual_seed(1000 + c)
+        a = torch.empty(n, dtype=torch.float32, device=dev).normal_(0.0, 0.01, generator=g)
+        re._zero_gaps(a)
+        arenas.append(a)
+    base16 = arenas[0].bfloat16()
+    bases = {"f32": base16.float(), "bf16": base16}
+    outs = {k: torch.empty_like(b) for k, b in bases.items()}
+    uploads = [pipe.forward_batch([re.view(a, i).cpu().numpy() for i in range(len(shapes))]) for a in arenas[1:]]
+    w = [float(v) for v in np.random.default_rng(0).random(C) + 0.5]
+    sums = torch.empty(n, dtype=torch.float64, device=dev)
+    np.random.seed(0)
+
+    def round_end(k):
+        acc = re.accumulator(sums=sums)
+        for items, wc in zip(uploads, w):
+            acc.add_upload(items, wc, delta=True, base_arena=bases[k])
+        re.finish(acc, base_arena=bases[k], payloads=False, out=outs[k])
+
+    def timed(fn, steps):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / steps
+
+    times = {k: [] for k in bases}
+    for _ in range(WINDOWS):
+        for k in bases:
+            times[k].append(timed(lambda: round_end(k), args.steps))
+    got = {}
+    for k in bases:
+        np.random.seed(0)   # finish() draws the seeds' offsets
+        round_end(k)
+        torch.cuda.synchronize()
+        got[k] = sums.clone()
+    same = bool(torch.equal(got["f32"].view(torch.int64), got["bf16"].view(torch.int64)) and
+                torch.equal(outs["f32"].bfloat16().view(torch.int16), outs["bf16"].view(torch.int16)))
+    # the last row passes alone: launch events of the plan over `reps` rounds
+    p, reps = re.plan, max(args.steps, 10)
+    big = sum(ln for t, i in enumerate(re.big) for P, ln in zip(p.dims[t], A.slice_plan(re.numels[i])[1]) if P > 1 << 15)
+    rows = {}
+    for k, which in (("f32", 3), ("bf16", 6)):
+        names = [l["name"] for l in p._launches(which)]
+        p.profile(True)
+        for _ in range(reps):
+            round_end(k)
+        torch.cuda.synchronize()
+        ms, calls = p.profile_collect(which)
+        p.profile(False)
+        b = 2 if k == "bf16" else 4   # per element: ws 4 + base b + sums 8 + 8 (the first upload reads no sums)
+        t = sum(m for m, nm in zip(ms, names) if "k_dec_acc_row" in nm) / calls
+        rows[k] = {"kernels": sorted({nm for nm in names if "k_dec_acc_row" in nm}), "calls": calls,
+                   "ms_per_upload": round(t, 5), "bytes_per_element": f"{20 + b} ({12 + b} on the first upload of the round)",
+                   "TBps": round(((20 + b) * (C - 1) + 12 + b) * big / C / t / 1e9, 3)}
+    L, st = _lib.lib(), torch.cuda.current_stream(dev).cuda_stream
+    delta = torch.empty(n, dtype=torch.float32, device=dev)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    fin = {}
+    for _ in range(reps):   # alternated
+        for k, fn in (("f32", L.ofl_wavg_finish), ("bf16", L.ofl_wavg_finish_bf16)):
+            ev[0].record()
+            _lib.check_agg(fn(sums.data_ptr(), 1.0, bases[k].data_ptr(), n, None, delta.data_ptr(), st))
+            ev[1].record()
+            torch.cuda.synchronize()
+            fin.setdefault(k, []).append(ev[0].elapsed_time(ev[1]))
+    finish = {k: {"ms": {"min": round(min(ts), 5), "max": round(max(ts), 5)}, "bytes_per_element": 22 if k == "bf16" else 24,
+                  "TBps_at_min": round((22 if k == "bf16" else 24) * n / min(ts) / 1e9, 3)} for k, ts in fin.items()}
+    print(json.dumps({"metric": "ms, round end from Eden-coded uploads (add_upload x C + finish, fused): bfloat16 base and "
+                                "model against the float32 round on the widened base",
+                      "workload": args.workload, "collaborators": C, "windows": WINDOWS, "steps_per_window": args.steps,
+                      "warmup": args.warmup, "same_bits": same, "large_slice_elements": big, "arena_elements": n,
+                      "ms_per_round": {k: {"min": round(min(ts), 4), "max": round(max(ts), 4),
+                                           "windows": [round(t, 4) for t in ts]} for k, ts in times.items()},
+                      "row_kernels": rows, "wavg_finish": finish}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="resnet50_fp32")
@@ -359,9 +463,14 @@ def main():
     ap.add_argument("--aggregation", choices=("adam", "yogi", "adagrad"), help="only the streamed FedOpt round end A/B")
     ap.add_argument("--upload-stream", action="store_true",
                     help="only the upload-streamed round end A/B: add_upload(fused=False | True) x C + finish")
+    ap.add_argument("--bf16", action="store_true", help="with --upload-stream: the bfloat16 round against the float32 one")
     args = ap.parse_args()
     if args.lossy_ingest:
         return lossy_ingest(args)
+    if args.bf16:
+        if not args.upload_stream:
+            ap.error("--bf16 goes with --upload-stream")
+        return upload_stream_bf16(args)
     if args.upload_stream:
         return upload_stream(args)
     if args.aggregation:
