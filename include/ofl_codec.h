@@ -199,6 +199,39 @@ int ofl_eden_decode_add(ofl_eden_plan_t plan, const uint8_t* planes_arena, const
 int ofl_eden_decode_accumulate(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uint32_t* seeds,
                                const float* scales, const float* base_arena /* nullable */, double w, int first,
                                double* sums, float* y_small, void* ws, size_t ws_bytes, void* stream);
+/* decode fused with the FedOpt gradient (ofl_adaptive_accumulate): one
+ * collaborator's planes straight into the float32 gradient arena g (the
+ * plan's layout).  The plan's decode schedule runs as it is -- the same waves,
+ * streams, fork / join and workspace (ofl_eden_plan_workspace_bytes) -- but
+ * the last row pass of the slices above 2^15 elements (k_dec_ada_rowC /
+ * k_dec_ada_rowC2 in place of k_dec_rowC / k_dec_rowC2) does not store y: per
+ * element i below the tensor's length, one float32 rounding per line,
+ *     x = delta ? base[i] + decoded[i] : decoded[i]    (ofl_eden_decode_add's float32 bits)
+ *     t = w * (base[i] - x)
+ *     g[i] = (first ? +0.0f : g[i]) + t
+ * i.e. ofl_adaptive_accumulate's operations on ofl_eden_decode_add's y, the
+ * same bits (the first add is kept: a -0.0 product becomes +0.0; base -
+ * (base + decoded) is not simplified), without y's 8 B/element round trip
+ * through HBM and without the arena-wide accumulate launch: 16 B/element in
+ * the pass (12 on the first upload) where the two launches move 28.
+ * base is the gradient base and is required; delta != 0: it is also the
+ * upload's apply-delta base (an upload whose apply-delta base is another
+ * arena takes ofl_eden_decode_add and ofl_adaptive_accumulate).  w: already
+ * rounded to float32.  Call in the collaborators' order.
+ * Slices of at most 2^15 elements keep their decode kernels and write
+ * (delta ? base + decoded : decoded) into y_small (float32, the plan's
+ * layout, written on those slices' ranges only); the caller folds them, and
+ * whatever the codec does not touch, with ofl_adaptive_accumulate_ranges.
+ * Nothing of g outside the large slices' valid elements is read or written,
+ * and nothing of base at or past a tensor's length is read.
+ * Null planes / seeds / scales / base / g: OFL_EINVAL; null y_small:
+ * OFL_EINVAL when the plan has a slice of at most 2^15 elements; nothing is
+ * launched then.  Async and graph-capturable after the plan's first use, as
+ * decode. */
+int ofl_eden_decode_adaptive_accumulate(ofl_eden_plan_t plan, const uint8_t* planes_arena, const uint32_t* seeds,
+                                        const float* scales, const float* base /* required */, int delta,
+                                        float w /* already float32 */, int first, float* g, float* y_small, void* ws,
+                                        size_t ws_bytes, void* stream);
 /* encode from and decode into bfloat16 arenas (bf16 passed as uint16_t; the
  * plan's layout in elements, 2 bytes each).  The plan's schedules run as they
  * are -- the same waves, streams, fork / join and workspace
@@ -384,7 +417,10 @@ int ofl_side_stream(int index, void** stream);
  * range launches of the small slices' side arena are not listed), 6 decode
  * into the sums against a bf16 base (ofl_eden_decode_accumulate_bf16: list
  * 3 with the row passes' bf16 names and a 2-byte base; the side arena's fold
- * is not listed). */
+ * is not listed), 7 decode into the FedOpt gradient
+ * (ofl_eden_decode_adaptive_accumulate: list 3 with the names k_dec_ada_rowC /
+ * k_dec_ada_rowC2 and the bytes of an upload after the first -- intermediate
+ * 4, base 4, g 4 + 4 per element). */
 int ofl_eden_plan_profile(ofl_eden_plan_t plan, int enable);
 int ofl_eden_plan_num_launches(ofl_eden_plan_t plan, int encode);
 int ofl_eden_plan_launch_info(ofl_eden_plan_t plan, int encode, int idx, char* name, int cap,
@@ -756,8 +792,19 @@ int ofl_adaptive_step(int ncollab, const float* const* xs, const float* weights,
  *                 itself).  g, base, p, v (and m) are required.  Reads 20
  *                 (ADAGRAD 16) and writes 12 to 20 bytes per element.
  * Both: 16-byte vector body when every pointer is 16-byte aligned, else
- * scalar; one launch, async. */
+ * scalar; one launch, async.
+ * ofl_adaptive_accumulate_ranges  ofl_adaptive_accumulate on listed ranges only
+ *                 (starts [nranges] / dst [nranges + 1]: DEVICE tables as
+ *                 ofl_wavg_accumulate_ranges; nothing synchronises): the elements
+ *                 ofl_eden_decode_adaptive_accumulate leaves to the caller -- the
+ *                 slices of at most 2^15 elements and the tensors the codec does
+ *                 not touch.  x, base and g are whole arenas; only the ranges
+ *                 are touched.  Arena quads that lie whole inside a range move
+ *                 in 16-byte accesses when all three are 16-byte aligned, a
+ *                 range's ragged ends element by element. */
 int ofl_adaptive_accumulate(const float* x, float w, const float* base, int first, int64_t n, float* g, void* stream);
+int ofl_adaptive_accumulate_ranges(const float* x, float w, const float* base, int first, int nranges,
+                                   const int64_t* starts, const int64_t* dst, int64_t total, float* g, void* stream);
 int ofl_adaptive_finish(const float* g, const float* base, int64_t n, float* p, float* m, float* v,
                         const ofl_adaptive_consts* k, float* agg_out, float* delta_out, void* stream);
 

@@ -22,7 +22,7 @@ EXPORTS = (
     "ofl_eden_plan_destroy", "ofl_eden_plan_set_schedule", "ofl_eden_plan_num_waves",
     "ofl_eden_plan_get_schedule", "ofl_eden_plan_set_row2", "ofl_eden_plan_set_pair", "ofl_eden_plan_set_sset", "ofl_eden_plan_set_fuse", "ofl_eden_plan_num_slices", "ofl_eden_plan_planes_bytes",
     "ofl_eden_plan_workspace_bytes", "ofl_eden_plan_tensor_info", "ofl_eden_plan_tensor_dims",
-    "ofl_eden_encode", "ofl_eden_encode_wavg", "ofl_eden_decode", "ofl_eden_decode_add", "ofl_eden_decode_accumulate", "ofl_eden_bf16_side_numel", "ofl_eden_encode_bf16", "ofl_eden_decode_add_bf16", "ofl_eden_decode_accumulate_bf16", "ofl_acc_side_ranges", "ofl_eden_roundtrip", "ofl_eden_roundtrip_wavg", "ofl_eden_roundtrip_workspace_bytes", "ofl_eden_encode_host", "ofl_eden_decode_host", "ofl_eden_encode_mapped", "ofl_eden_decode_mapped", "ofl_eden_encode_seeded", "ofl_copy_h2d_chunked", "ofl_eden_encode_host_x", "ofl_eden_decode_host_x", "ofl_copy_h2d_async", "ofl_copy_h2d_staged", "ofl_eden_plan_profile", "ofl_eden_plan_num_launches",
+    "ofl_eden_encode", "ofl_eden_encode_wavg", "ofl_eden_decode", "ofl_eden_decode_add", "ofl_eden_decode_accumulate", "ofl_eden_decode_adaptive_accumulate", "ofl_eden_bf16_side_numel", "ofl_eden_encode_bf16", "ofl_eden_decode_add_bf16", "ofl_eden_decode_accumulate_bf16", "ofl_acc_side_ranges", "ofl_eden_roundtrip", "ofl_eden_roundtrip_wavg", "ofl_eden_roundtrip_workspace_bytes", "ofl_eden_encode_host", "ofl_eden_decode_host", "ofl_eden_encode_mapped", "ofl_eden_decode_mapped", "ofl_eden_encode_seeded", "ofl_copy_h2d_chunked", "ofl_eden_encode_host_x", "ofl_eden_decode_host_x", "ofl_copy_h2d_async", "ofl_copy_h2d_staged", "ofl_eden_plan_profile", "ofl_eden_plan_num_launches",
     "ofl_eden_plan_launch_info", "ofl_eden_plan_launch_detail", "ofl_eden_plan_profile_collect", "ofl_serial_sum_f32", "ofl_serial_sum_f32_mt", "ofl_serial_sum_copy_f32",
     "ofl_serial_sum_f64", "ofl_host_copy_many", "ofl_serial_sums_many", "ofl_lossy_last_error", "ofl_lossy_workspace_bytes", "ofl_kmeans1d_fit",
     "ofl_kmeans1d_batch_workspace_bytes", "ofl_kmeans1d_batch", "ofl_kmeans1d_batch_tab",
@@ -35,7 +35,7 @@ EXPORTS = (
     "ofl_wavg_points_workspace_bytes", "ofl_wavg_delta_points", "ofl_apply_delta",
     "ofl_apply_delta_ranges", "ofl_wavg_delta32_ranges", "ofl_wavg_accumulate_ranges", "ofl_sub_f32_f64",
     "ofl_median_delta", "ofl_gmedian_workspace_bytes", "ofl_gmedian_delta", "ofl_agg_delta_seeds",
-    "ofl_adaptive_step", "ofl_adaptive_accumulate", "ofl_adaptive_finish",
+    "ofl_adaptive_step", "ofl_adaptive_accumulate", "ofl_adaptive_accumulate_ranges", "ofl_adaptive_finish",
     "ofl_gzip_last_error", "ofl_gzip_ranks_workspace_bytes", "ofl_gzip_ranks_bound", "ofl_gzip_ranks", "ofl_gzip_ranks_to", "ofl_gzip_label_to", "ofl_side_stream",
     "ofl_gzip_ranks_batch_workspace_bytes", "ofl_gzip_ranks_batch_bound", "ofl_gzip_ranks_batch",
     "ofl_gunzip_members", "ofl_gzip_member_index", "ofl_inflate_members", "ofl_inflate_tlz_workspace_bytes",
@@ -89,6 +89,8 @@ def _bind(L):
     L.ofl_eden_decode_add.restype = i32
     L.ofl_eden_decode_accumulate.argtypes = [vp, vp, vp, vp, vp, ctypes.c_double, i32, vp, vp, vp, sz, vp]
     L.ofl_eden_decode_accumulate.restype = i32
+    L.ofl_eden_decode_adaptive_accumulate.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.c_float, i32, vp, vp, vp, sz, vp]
+    L.ofl_eden_decode_adaptive_accumulate.restype = i32
     L.ofl_eden_bf16_side_numel.argtypes = [vp]
     L.ofl_eden_bf16_side_numel.restype = i64
     L.ofl_eden_encode_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp]
@@ -222,6 +224,8 @@ def _bind(L):
     L.ofl_adaptive_step.restype = i32
     L.ofl_adaptive_accumulate.argtypes = [vp, ctypes.c_float, vp, i32, i64, vp, vp]
     L.ofl_adaptive_accumulate.restype = i32
+    L.ofl_adaptive_accumulate_ranges.argtypes = [vp, ctypes.c_float, vp, i32, i32, vp, vp, i64, vp, vp]
+    L.ofl_adaptive_accumulate_ranges.restype = i32
     L.ofl_adaptive_finish.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     L.ofl_adaptive_finish.restype = i32
     L.ofl_gzip_last_error.restype = ctypes.c_char_p

@@ -770,7 +770,9 @@ class WavgAccumulator:
             if self._scratch is None:
                 self._scratch = re._empty_arena()
             # the scratch: ingest's arena on the _fz ranges only (raw tensors, small slices)
-            re._ingest_eden(items, bufs, base_arena if delta else None, self._scratch, fold=(self.sums, w, c == 0))
+            re._ingest_eden(items, bufs, base_arena if delta else None, self._scratch,
+                            fold=lambda planes, seeds, scales, out, ws, base: re.plan.decode_accumulate(
+                                planes, seeds, scales, self.sums, w, c == 0, out, ws, base=base))
             _lib.check_agg(_lib.lib().ofl_wavg_accumulate_ranges(self._scratch.data_ptr(), w, 1 if c == 0 else 0,
                                                                   *re._fz.args, self.sums.data_ptr(), _stream(dev)))
             if re.single:
@@ -837,14 +839,53 @@ class AdaptiveAccumulator:
         """_f32_weights' rule, and its errors, on the next collaborator's weight."""
         return _f32_weights(f"{self.re.aggregation} accumulator, collaborator {len(self.weights)}", [weight])[0]
 
-    def add_upload(self, items, weight, lossless=False, delta=True, base_arena=None):
-        """re.ingest(items, ...) into this accumulator's own scratch arena,
-        then add(that, weight): one collaborator's upload as it arrives."""
+    def add_upload(self, items, weight, lossless=False, delta=True, base_arena=None, fused=None):
+        """One collaborator's upload as it arrives.  fused=False:
+        re.ingest(items, ...) into this accumulator's own scratch arena, then
+        add(that, weight).  fused=True: an Eden-coded upload (lossless=False,
+        a layout with tensors above dim_threshold) whose apply-delta base is
+        the accumulator's own (delta=False, or base_arena the same storage as
+        `base`) is decoded straight into the gradient --
+        ofl_eden_decode_adaptive_accumulate: the slices above 2^15 elements
+        never cross HBM as float32, and there is no arena-wide accumulate
+        launch; the raw tensors and the slices of at most 2^15 elements go
+        through the scratch and one ofl_adaptive_accumulate_ranges.  The
+        gradient's bits on every tensor are the unfused path's, so the two may
+        be mixed within a round; its alignment gaps, which carry no meaning,
+        are zeroed on the first upload.  CodecError where that does not apply.
+        fused=None (default): fused where it applies.  Every check of
+        ingest() and add() raises before anything is launched."""
         if self.finished:
             raise _lib.CodecError("accumulator: add_upload() after finish()")
-        self._weight32(weight)  # refused before the ingest launches anything
-        self._scratch = self.re.ingest(items, lossless=lossless, delta=delta, base_arena=base_arena, out=self._scratch)
-        self.add(self._scratch, weight)
+        re = self.re
+        dev = resolve_device(getattr(re, "device", None))
+        same_base = not delta or (base_arena is not None and base_arena.dtype == self.base.dtype
+                                  and base_arena.data_ptr() == self.base.data_ptr())
+        applies = re._lossy is None and not lossless and re.plan is not None and same_base
+        if fused and not applies:
+            raise _lib.CodecError("add_upload(fused=True) takes an Eden pipeline's lossy_compressed upload into a "
+                                  "layout with tensors above dim_threshold, with delta=False or the accumulator's own "
+                                  "base as base_arena")
+        w32 = self._weight32(weight)  # refused before the ingest launches anything
+        if not applies or (fused is not None and not fused):
+            self._scratch = re.ingest(items, lossless=lossless, delta=delta, base_arena=base_arena, out=self._scratch)
+            return self.add(self._scratch, weight)
+        items, bufs = re._ingest_begin(items, "eden", delta, base_arena, self._scratch)
+        first = not self.weights
+        with torch.cuda.device(dev):
+            if self._scratch is None:
+                self._scratch = re._empty_arena()
+            # the scratch: ingest's arena on the _fz ranges only (raw tensors, small slices)
+            re._ingest_eden(items, bufs, self.base if delta else None, self._scratch,
+                            fold=lambda planes, seeds, scales, out, ws, base: re.plan.decode_adaptive_accumulate(
+                                planes, seeds, scales, self.sums, w32, first, out, ws, base=self.base,
+                                delta=base is not None))
+            _lib.check_agg(_lib.lib().ofl_adaptive_accumulate_ranges(
+                self._scratch.data_ptr(), float(np.float32(w32)), self.base.data_ptr(), 1 if first else 0, *re._fz.args,
+                self.sums.data_ptr(), _stream(dev)))
+            if first and re._gap_idx is not None:
+                self.sums.index_fill_(0, re._gap_idx, 0.0)
+        self.weights.append(weight)
 
 
 class RoundEnd:
@@ -1157,9 +1198,10 @@ class RoundEnd:
     def _ingest_eden(self, items, bufs, base, out, fold=None):
         """EdenPipeline's payloads: the big tensors' planes, scales and seeds in
         one H2D and one batch decode (which adds the base); the rest are raw.
-        fold = (sums, weight, first), WavgAccumulator.add_upload's fused path:
-        the batch decode folds the slices above 2^15 elements into sums
-        (EdenPlan.decode_accumulate) and writes only the smaller ones to out."""
+        fold(planes, seeds, scales, out, ws, base), the accumulators'
+        add_upload(fused=True): it runs the batch decode that folds the slices
+        above 2^15 elements into the accumulator (EdenPlan.decode_accumulate /
+        decode_adaptive_accumulate) and writes only the smaller ones to out."""
         dev, p = self.device, self.plan
         raw = [i for i, n in enumerate(self.numels) if 0 < n <= self.dim_threshold]
         off_scales = (p.planes_bytes + 255) // 256 * 256 if p is not None else 0
@@ -1194,7 +1236,7 @@ class RoundEnd:
                 # the staging is free once its copies have run: the next upload's
                 # staging does not wait for this one's decode and fold as well
                 self._ingest_sent()
-                p.decode_accumulate(planes, seeds_d, scales_d, *fold, out, self._codec_ws, base=base)
+                fold(planes, seeds_d, scales_d, out, self._codec_ws, base)
         if fold is None:
             self._ingest_sent()
         if raw and base is not None:

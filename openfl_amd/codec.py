@@ -238,6 +238,38 @@ class EdenPlan:
         not the plan's, is not listed)."""
         return self._launches(6 if bf16 else 3)
 
+    def decode_adaptive_accumulate(self, planes, seeds, scales, g, weight32, first, y_small, ws, stream=None, base=None,
+                                   delta=True):
+        """decode (+ base) folded into the FedOpt gradient
+        (ofl_eden_decode_adaptive_accumulate): on the slices above 2^15
+        elements g = (+0.0 if first else g) + weight32 * (base - y), float32
+        with one rounding per operation, for the y that decode(..., base=base
+        if delta else None) would write, which is not written -- the bits of
+        aggregation.adaptive_accumulate on that y.  g, base: float32
+        [arena_numel], base the gradient base (required) and, with delta, the
+        upload's apply-delta base too; weight32: already rounded to float32.
+        y_small: float32[arena_numel], written with decode's y on the slices
+        of at most 2^15 elements only (for ofl_adaptive_accumulate_ranges);
+        None is allowed when the plan has none."""
+        if g is None or base is None:
+            raise _lib.CodecError("decode_adaptive_accumulate needs g and the gradient base")
+        for a in (g, base, y_small):
+            if a is not None:
+                self._check(a, torch.float32, self.arena_numel)
+        self._check(planes, torch.uint8, self.planes_bytes)
+        self._check(scales, torch.float32, self.n_slices)
+        self._check(seeds, torch.int32, len(self.numels))
+        st = stream if stream is not None else torch.cuda.current_stream(g.device)
+        _lib.check(self._L.ofl_eden_decode_adaptive_accumulate(
+            self._h, planes.data_ptr(), seeds.data_ptr(), scales.data_ptr(), base.data_ptr(), 1 if delta else 0,
+            float(np.float32(weight32)), 1 if first else 0, g.data_ptr(),
+            y_small.data_ptr() if y_small is not None else None, ws.data_ptr() if ws is not None else None,
+            ws.numel() if ws is not None else 0, st.cuda_stream))
+
+    def adaptive_launches(self):
+        """The launches of a decode_adaptive_accumulate, as launches() reports them."""
+        return self._launches(7)
+
     def roundtrip(self, x_arena, seeds, y_arena, scales, ws, stream=None, base=None):
         """y_arena = decode(encode(x_arena)) (+ base when given) and the
         encode's scales, bit for bit, without the planes
@@ -297,8 +329,9 @@ class EdenPlan:
         """-> (per-launch summed ms, number of recorded calls).  encode: False
         / True, 2 for the round trip's launches, 3 for decode_accumulate's,
         4 / 5 for encode's / decode's with bfloat16 arenas, 6 for
-        decode_accumulate's against a bfloat16 base."""
-        which = int(encode) if encode in (2, 3, 4, 5, 6) else 1 if encode else 0
+        decode_accumulate's against a bfloat16 base, 7 for
+        decode_adaptive_accumulate's."""
+        which = int(encode) if encode in (2, 3, 4, 5, 6, 7) else 1 if encode else 0
         n = self._L.ofl_eden_plan_num_launches(self._h, which)
         ms = np.zeros(max(n, 1), np.float64)
         calls = ctypes.c_int()

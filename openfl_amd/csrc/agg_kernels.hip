@@ -1455,6 +1455,39 @@ __global__ __launch_bounds__(kNT) OFL_NO_PACKED_F32 void k_adaptive_finish(AdaFi
     quads_then_tail(a.io.n, vec, [&](int64_t i) { ada_fin_quad(a, i); }, [&](int64_t i) { ada_fin_elem(a, i); });
 }
 
+// k_adaptive_accumulate (ada_acc) on listed ranges only: the elements a fused
+// decode into the gradient does not fold itself
+// (ofl_eden_decode_adaptive_accumulate: slices of <= 2^15 elements and the
+// tensors the codec does not touch).  A lane takes 4 consecutive packed
+// elements.  Within a range, an arena quad (elements 4q .. 4q + 3) that lies
+// whole inside it is one 16-byte access of x, base and g by the lane that
+// holds its first element -- a run of 4 packed elements holds at most one
+// such first element -- and the range's ragged ends go element by element,
+// so every listed element is folded exactly once and nothing else is touched.
+template <bool FIRST>
+__global__ __launch_bounds__(kNT) OFL_NO_PACKED_F32 void k_adaptive_accumulate_ranges(AdaAccArgs a, Ranges rg, int vec) {
+    const int64_t total = rg.total();
+    for (int64_t j0 = 4 * ((int64_t)blockIdx.x * kNT + threadIdx.x); j0 < total; j0 += 4 * (int64_t)gridDim.x * kNT) {
+        int64_t i;
+        int r = rg.find(j0, i);
+        for (int64_t j = j0; j < j0 + 4 && j < total; ++j) {
+            while (j >= rg.dst[r + 1]) ++r;  // into the next range that has elements
+            i = rg.start[r] + (j - rg.dst[r]);
+            const int64_t q0 = i & ~(int64_t)3;
+            const bool whole = vec && q0 >= rg.start[r] && q0 + 4 <= rg.start[r] + (rg.dst[r + 1] - rg.dst[r]);
+            if (!whole) {
+                ada_acc_elem<FIRST>(a, i);
+            } else if (i == q0) {
+                const float4 x = load_once(a.x + i), b = *reinterpret_cast<const float4*>(a.base + i);
+                const float4 g = FIRST ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(a.g + i);
+                *reinterpret_cast<float4*>(a.g + i) =
+                    make_float4(ada_acc<FIRST>(a.w, b.x, x.x, g.x), ada_acc<FIRST>(a.w, b.y, x.y, g.y),
+                                ada_acc<FIRST>(a.w, b.z, x.z, g.z), ada_acc<FIRST>(a.w, b.w, x.w, g.w));
+            }
+        }
+    }
+}
+
 }  // namespace agg
 
 extern "C" {
@@ -1467,6 +1500,19 @@ int ofl_adaptive_accumulate(const float* x, float w, const float* base, int firs
     const dim3 grid(grid_for(n, 4 * agg::kAdaAccQ));
     hipLaunchKernelGGL(first ? agg::k_adaptive_accumulate<true> : agg::k_adaptive_accumulate<false>, grid,
                        dim3(agg::kNT), 0, static_cast<hipStream_t>(stream), a, vec);
+    AHIP(hipGetLastError());
+    return OFL_OK;
+}
+
+int ofl_adaptive_accumulate_ranges(const float* x, float w, const float* base, int first, int nranges,
+                                   const int64_t* starts, const int64_t* dst, int64_t total, float* g, void* stream) {
+    if (nranges < 1 || total <= 0) return OFL_OK;
+    if (!x || !base || !g || !starts || !dst) return afail(OFL_EINVAL, "adaptive_accumulate_ranges: bad arguments");
+    const agg::AdaAccArgs a{x, base, g, w, total};
+    const int vec = aligned16(&x, 1, base, g);
+    const dim3 grid(grid_for(total, 4));
+    hipLaunchKernelGGL(first ? agg::k_adaptive_accumulate_ranges<true> : agg::k_adaptive_accumulate_ranges<false>, grid,
+                       dim3(agg::kNT), 0, static_cast<hipStream_t>(stream), a, agg::Ranges{starts, dst, nranges}, vec);
     AHIP(hipGetLastError());
     return OFL_OK;
 }

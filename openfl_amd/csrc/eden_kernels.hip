@@ -113,6 +113,8 @@ struct KArgs {
         uint8_t* pout;      // planes out (encode)
         double* sums;       // the sums arena (decode-accumulate)
         uint16_t* y16;      // the bf16 arena out (ofl_eden_decode_add_bf16, eden_bf16.h)
+        float* g;           // the FedOpt gradient arena (ofl_eden_decode_adaptive_accumulate, eden_dec_ada.h:
+                            // its base is wbase, yadd that or null, its first flag acc_first)
     };
     const uint32_t* seeds;
     float* scales;          // encode: out
@@ -139,6 +141,7 @@ struct KArgs {
     union {
         double wsum;        // NumPy's float64 sum of the weights
         double acc_w;       // the collaborator's weight (decode-accumulate)
+        float ada_w;        // the same, already float32 (decode into the gradient)
     };
     int32_t wc;             // collaborators (1..16)
     int32_t acc_first;      // decode-accumulate: store the product instead of adding it
@@ -2342,6 +2345,8 @@ __global__ __launch_bounds__(256) void k_finalize(KArgs a) {
 #include "eden_bf16.h"
 // decode's last row pass into the sums against a bf16 base and the side arena's fold, after it
 #include "eden_dec_acc_bf16.h"
+// decode's last row pass into the FedOpt gradient, after it
+#include "eden_dec_ada.h"
 
 }  // namespace ofl
 
@@ -2368,7 +2373,7 @@ struct ofl_eden_plan {
     const char* rt_err = nullptr;  // why the plan has none (ofl_eden_roundtrip reports it)
     // profiling: events around every launch of every call while enabled
     bool prof = false;
-    std::vector<std::vector<hipEvent_t>> prof_ev[7];  // [dec, enc, round trip, decode-accumulate, bf16 enc, bf16 dec, bf16 decode-accumulate][call][launch+1]
+    std::vector<std::vector<hipEvent_t>> prof_ev[8];  // [dec, enc, round trip, decode-accumulate, bf16 enc, bf16 dec, bf16 decode-accumulate, decode into the gradient][call][launch+1]
     std::vector<hipEvent_t> ev_pool;
     ofl::SliceDesc* d_slices = nullptr;
     ofl::SliceDesc* d_rt_slices = nullptr;  // rt.slices
@@ -2481,12 +2486,19 @@ constexpr KernelEntry kAcc16Kernels[eden::ACC_KERNEL_COUNT] = {
     {eden::KERNEL_COUNT, ofl::k_dec_acc_rowC2_bf16, ofl::kRowNT, ofl::kRow2Smem},
 };
 
+// decode into the FedOpt gradient's kernels, one entry per eden::AdaKernelId
+constexpr KernelEntry kAdaKernels[eden::ADA_KERNEL_COUNT] = {
+    {eden::KERNEL_COUNT, ofl::k_dec_ada_rowC, ofl::kRowNT, ofl::kRowSmemA},
+    {eden::KERNEL_COUNT, ofl::k_dec_ada_rowC2, ofl::kRowNT, ofl::kRow2Smem},
+};
+
 hipError_t set_all_attrs() {
     const std::pair<const KernelEntry*, int> tabs[] = {{kKernels, (int)eden::KERNEL_COUNT},
                                                        {kRtKernels, (int)eden::RT_KERNEL_COUNT},
                                                        {kAccKernels, (int)eden::ACC_KERNEL_COUNT},
                                                        {kBf16Kernels, (int)eden::BF16_KERNEL_COUNT},
-                                                       {kAcc16Kernels, (int)eden::ACC_KERNEL_COUNT}};
+                                                       {kAcc16Kernels, (int)eden::ACC_KERNEL_COUNT},
+                                                       {kAdaKernels, (int)eden::ADA_KERNEL_COUNT}};
     for (const auto& [tab, n] : tabs)
         for (int i = 0; i < n; ++i) {
             const KernelEntry& k = tab[i];
@@ -2498,7 +2510,7 @@ hipError_t set_all_attrs() {
 }
 
 // which of a plan's launch lists a call runs (the ABI's `encode` argument)
-enum { RUN_DEC = 0, RUN_ENC = 1, RUN_RT = 2, RUN_ACC = 3, RUN_ENC16 = 4, RUN_DEC16 = 5, RUN_ACC16 = 6, RUN_COUNT };
+enum { RUN_DEC = 0, RUN_ENC = 1, RUN_RT = 2, RUN_ACC = 3, RUN_ENC16 = 4, RUN_DEC16 = 5, RUN_ACC16 = 6, RUN_ADA = 7, RUN_COUNT };
 int num_launches(const ofl_eden_plan* pl, int which) {
     const bool enc = which == RUN_ENC || which == RUN_ENC16;
     return (int)(which == RUN_RT ? pl->rt.list.size() : enc ? pl->p.enc.size() : pl->p.dec.size());
@@ -2514,10 +2526,11 @@ struct Picked {
     bool acc;  // a decode-accumulate row launch (its bytes: eden::acc_bytes_moved)
     bool acc16;  // the same against a bf16 base (eden::acc16_bytes_moved)
     bool bf;   // a row launch on a bf16 arena (its bytes: eden::bf16_bytes_moved / _alg)
+    bool ada;  // a row launch into the FedOpt gradient (eden::ada_bytes_moved)
 };
 const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, bool wavg, bool planes8, Picked& p) {
     const char* err = nullptr;
-    int rt = -1, acc = -1, bf = -1;
+    int rt = -1, acc = -1, bf = -1, ada = -1;
     if (which == RUN_ENC16 || which == RUN_DEC16) {
         p.l = &(which == RUN_ENC16 ? pl->p.enc : pl->p.dec)[idx];
         err = eden::bf16_resolve(pl->p, *p.l, which == RUN_ENC16, ncu, planes8, p.r, bf);
@@ -2530,6 +2543,9 @@ const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, boo
     } else if (which == RUN_ACC || which == RUN_ACC16) {
         p.l = &pl->p.dec[idx];
         err = eden::acc_resolve(pl->p, *p.l, ncu, planes8, p.r, acc);
+    } else if (which == RUN_ADA) {
+        p.l = &pl->p.dec[idx];
+        err = eden::ada_resolve(pl->p, *p.l, ncu, planes8, p.r, ada);
     } else {
         p.l = &(which == RUN_ENC ? pl->p.enc : pl->p.dec)[idx];
         err = eden::resolve(pl->p, *p.l, which == RUN_ENC, ncu, wavg, planes8, p.r);
@@ -2538,6 +2554,12 @@ const char* resolve_at(const ofl_eden_plan* pl, int which, int idx, int ncu, boo
     p.acc16 = acc >= 0 && which == RUN_ACC16;
     p.acc = acc >= 0 && !p.acc16;
     p.bf = bf >= 0;
+    p.ada = ada >= 0;
+    if (p.ada) {
+        p.k = &kAdaKernels[ada];
+        p.name = eden::kAdaKernelName[ada];
+        return nullptr;
+    }
     p.k = rt >= 0 ? &kRtKernels[rt] : p.acc16 ? &kAcc16Kernels[acc] : acc >= 0 ? &kAccKernels[acc]
           : bf >= 0 ? &kBf16Kernels[bf] : &kKernels[p.r.id];
     p.name = rt >= 0 ? eden::kRtKernelName[rt] : p.acc16 ? eden::kAcc16KernelName[acc] : acc >= 0 ? eden::kAccKernelName[acc]
@@ -2923,6 +2945,31 @@ int ofl_eden_decode_accumulate(ofl_eden_plan_t pl, const uint8_t* planes_arena, 
     a.acc_w = w;
     a.acc_first = first ? 1 : 0;
     return run(pl, RUN_ACC, a, static_cast<hipStream_t>(stream));
+}
+
+int ofl_eden_decode_adaptive_accumulate(ofl_eden_plan_t pl, const uint8_t* planes_arena, const uint32_t* seeds,
+                                        const float* scales, const float* base, int delta, float w, int first, float* g,
+                                        float* y_small, void* ws, size_t ws_bytes, void* stream) {
+    if (!pl) return fail(OFL_EINVAL, "null plan");
+    if (!planes_arena || !seeds || !scales || !base || !g)
+        return fail(OFL_EINVAL, "decode_adaptive_accumulate: null argument");
+    if ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(g)) & 3u)
+        return fail(OFL_EINVAL, "decode_adaptive_accumulate: misaligned argument");
+    if (!y_small && eden::has_small_slice(pl->p))
+        return fail(OFL_EINVAL, "decode_adaptive_accumulate: the plan has slices of at most 2^15 elements, which need y_small");
+    ofl::KArgs a;
+    int rc = prep_args(pl, a, ws, ws_bytes);
+    if (rc) return rc;
+    a.pin = planes_arena;
+    a.xout = y_small;  // the tiny / small slices' decode kernels alone write it
+    a.yadd = delta ? base : nullptr;  // theirs, and the row passes' delta flag
+    a.wbase = base;
+    a.seeds = seeds;
+    a.scales_in = scales;
+    a.g = g;
+    a.ada_w = w;
+    a.acc_first = first ? 1 : 0;
+    return run(pl, RUN_ADA, a, static_cast<hipStream_t>(stream));
 }
 
 // The small slices' range tables and the bf16 calls' slice table on the
@@ -3354,9 +3401,9 @@ int ofl_eden_plan_launch_info(ofl_eden_plan_t pl, int encode, int idx, char* nam
     if (name && cap > 0) snprintf(name, (size_t)cap, "%s", p.name);
     if (blocks) *blocks = p.l->blocks;
     if (bytes_moved)
-        *bytes_moved = p.acc16 ? eden::acc16_bytes_moved(*p.l) : p.acc ? eden::acc_bytes_moved(*p.l)
+        *bytes_moved = p.ada ? eden::ada_bytes_moved(*p.l) : p.acc16 ? eden::acc16_bytes_moved(*p.l) : p.acc ? eden::acc_bytes_moved(*p.l)
                        : p.bf ? eden::bf16_bytes_moved(*p.l) : p.l->bytes_moved;
-    if (bytes_alg) *bytes_alg = p.acc || p.acc16 ? 0 : p.bf ? eden::bf16_bytes_alg(*p.l) : p.l->bytes_alg;
+    if (bytes_alg) *bytes_alg = p.acc || p.acc16 || p.ada ? 0 : p.bf ? eden::bf16_bytes_alg(*p.l) : p.l->bytes_alg;
     return OFL_OK;
 }
 

@@ -26,6 +26,10 @@ One process, windows alternated (A B A B A B, the minimum and the spread of each
   --upload-stream   instead: the round end from Eden-coded uploads, add_upload x
               C + finish, the decode fused with the accumulate against ingest +
               add, and the last row passes alone (upload_stream).
+  --aggregation KIND --upload-stream   instead: that A/B for the FedOpt round,
+              the decode fused with the gradient accumulate, k_dec_ada_rowC /
+              k_dec_ada_rowC2 beside k_dec_rowC / k_dec_rowC2 + k_adaptive_accumulate
+              (upload_stream_adaptive).
   --upload-stream --bf16   instead: that round with a bfloat16 base and model
               against the float32 round on the widened base, same plans, and
               k_dec_acc_rowC2_bf16 / ofl_wavg_finish_bf16 beside their float32
@@ -352,6 +356,113 @@ def upload_stream(args):
           flush=True)
 
 
+def upload_stream_adaptive(args):
+    """--aggregation KIND --upload-stream: the FedOpt round end fed with
+    Eden-coded uploads, add_upload x C + finish, with the decode folded into
+    the gradient (fused=True: ofl_eden_decode_adaptive_accumulate) against
+    ingest + add (fused=False), alternated windows in one process; then, under
+    the plan's launch events, the last row passes alone: k_dec_ada_rowC /
+    k_dec_ada_rowC2 (ws 4 + base 4 + g 4 + 4 B per element; the first upload
+    reads no g) beside k_dec_rowC / k_dec_rowC2 (ws 4 + base 4 + y 4) plus
+    k_adaptive_accumulate over the arena (x 4 + base 4 + g 4 + 4), both by
+    bytes over time."""
+    import torch
+    from openfl_amd import aggregation as A
+    from openfl_amd.pipelines import EdenPipeline
+    from openfl_amd.workloads import WORKLOADS
+    dev = torch.device("cuda", 0)
+    shapes = [tuple(s) for _, s in WORKLOADS[args.workload]()]
+    pipe = EdenPipeline(n_bits=8, device=dev, seed_mode="fast")
+    re = A.RoundEnd(pipe, shapes, dev, aggregation=args.aggregation)
+    C, n = args.collaborators, re.arena_numel
+    g = torch.Generator(device=dev)
+    arenas = []
+    for c in range(C + 1):
+        g.manual_seed(1000 + c)
+        a = torch.empty(n, dtype=torch.float32, device=dev).normal_(0.0, 0.01, generator=g)
+        re._zero_gaps(a)
+        arenas.append(a)
+    base = arenas[0]
+    re.init_optimizer(base)
+    uploads = [pipe.forward_batch([re.view(a, i).cpu().numpy() for i in range(len(shapes))]) for a in arenas[1:]]
+    w = [float(v) for v in np.random.default_rng(0).random(C) + 0.5]
+    out, grad = torch.empty_like(base), torch.empty_like(base)
+    np.random.seed(0)
+
+    def adds(fused):
+        acc = re.accumulator(sums=grad, base_arena=base)
+        for items, wc in zip(uploads, w):
+            acc.add_upload(items, wc, delta=True, base_arena=base, fused=fused)
+        return acc
+
+    def timed(fn, steps):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / steps
+
+    fns = {"unfused": lambda: re.finish(adds(False), payloads=False, out=out),
+           "fused": lambda: re.finish(adds(True), payloads=False, out=out)}
+    times = {k: [] for k in fns}
+    for _ in range(WINDOWS):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, args.steps))
+    grads = {}
+    for k in fns:
+        adds(k == "fused")
+        torch.cuda.synchronize()
+        grads[k] = grad.clone()
+    same = all(torch.equal(grads["fused"][o:o + m].view(torch.int32), grads["unfused"][o:o + m].view(torch.int32))
+               for o, m in zip(re.offsets, re.numels))
+    # the last row passes alone: launch events of the plan over `reps` rounds
+    p, reps = re.plan, max(args.steps, 10)
+    big = sum(ln for t, i in enumerate(re.big) for P, ln in zip(p.dims[t], A.slice_plan(re.numels[i])[1]) if P > 1 << 15)
+    rows = {}
+    for k, which, rowk in (("unfused", 0, ("ofl::k_dec_rowC", "ofl::k_dec_rowC2")),
+                           ("fused", 7, ("ofl::k_dec_ada_rowC", "ofl::k_dec_ada_rowC2"))):
+        names = [l["name"] for l in p._launches(which)]
+        p.profile(True)
+        for _ in range(reps):
+            fns[k]()
+        torch.cuda.synchronize()
+        ms, calls = p.profile_collect(which)
+        p.profile(False)
+        rows[k] = {"kernels": sorted({nm for nm in names if nm in rowk}), "calls": calls,
+                   "ms_per_upload": round(sum(m for m, nm in zip(ms, names) if nm in rowk) / calls, 5)}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    acc_ms = []
+    for _ in range(reps):
+        ev[0].record()
+        A.adaptive_accumulate(arenas[1], 1e-3, base, n, grad, False, device=dev)
+        ev[1].record()
+        torch.cuda.synchronize()
+        acc_ms.append(ev[0].elapsed_time(ev[1]))
+    t_acc = min(acc_ms)
+    t_un, t_fu = rows["unfused"]["ms_per_upload"], rows["fused"]["ms_per_upload"]
+    # per upload, averaged over a round of C: one first upload in C
+    b_un_row, b_fu = 12 * big, (16 * (C - 1) + 12) * big / C
+    print(json.dumps({
+        "metric": f"ms, {args.aggregation} round end from Eden-coded uploads: add_upload x C + finish, decode fused with "
+                  "the gradient accumulate against ingest + add",
+        "workload": args.workload, "collaborators": C, "windows": WINDOWS, "steps_per_window": args.steps,
+        "warmup": args.warmup, "wire_bytes_per_upload": sum(len(b) for b, _ in uploads[0]), "same_bits": same,
+        "ms_per_round": {k: {"min": round(min(ts), 4), "max": round(max(ts), 4), "windows": [round(t, 4) for t in ts]}
+                         for k, ts in times.items()},
+        "row_kernels": {
+            "large_slice_elements": big, "arena_elements": n,
+            "unfused": dict(rows["unfused"], bytes_per_element=12, TBps=round(b_un_row / t_un / 1e9, 3)),
+            "adaptive_accumulate_whole_arena": {"ms": round(t_acc, 5), "max_ms": round(max(acc_ms), 5),
+                                                "bytes_per_element": 16, "TBps": round(16 * n / t_acc / 1e9, 3)},
+            "unfused_row_plus_accumulate": {"ms": round(t_un + t_acc, 5), "bytes_per_element": 28,
+                                            "TBps": round((b_un_row + 16 * n) / (t_un + t_acc) / 1e9, 3)},
+            "fused": dict(rows["fused"], bytes_per_element="16 (12 on the first upload of the round)",
+                          TBps=round(b_fu / t_fu / 1e9, 3))}}), flush=True)
+
+
 def upload_stream_bf16(args):
     """--upload-stream --bf16: add_upload x C + finish with a bfloat16 base and a
     bfloat16 new model against the fused float32 round on the widened base --
@@ -472,7 +583,7 @@ def main():
             ap.error("--bf16 goes with --upload-stream")
         return upload_stream_bf16(args)
     if args.upload_stream:
-        return upload_stream(args)
+        return upload_stream_adaptive(args) if args.aggregation else upload_stream(args)
     if args.aggregation:
         return adaptive_stream(args)
 
